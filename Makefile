@@ -18,8 +18,8 @@ test:
 	$(PY) -m pytest tests -q -m "not gpu"
 test-gpu:
 	$(PY) -m pytest tests -q -m gpu
-bench:
-	$(PY) bench.py
+bench:                               # every section with its checks; `$(PY) bench.py` alone times the headline SGEMM
+	$(PY) bench.py --full
 sanitize:
 	$(PY) -m parallel_c_programs_amd.sanitize
 

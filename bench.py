@@ -1,6 +1,14 @@
 #!/usr/bin/env python3
-"""Headline benchmark: "TFLOPS SGEMM 8192^2 + GB/s reduce 1e9 f32, at 1/2/4/8 MI355X" (BASELINE.json), plus
-every other BASELINE.json north-star config measured at the same N in the same job.
+"""Headline benchmark: "TFLOPS SGEMM 8192^2 + GB/s reduce 1e9 f32, at 1/2/4/8 MI355X" (BASELINE.json), plus, with
+`--full`, every other BASELINE.json north-star config measured at the same N in the same job.
+
+A PLAIN run (`bench.py --gpus N --steps K --warmup W`) does only what the headline `value` needs: it sets up the
+SGEMM, warms it up, times EXACTLY K steps and prints the line (`value`, `ms_per_step` = one timed SGEMM step); no
+check, no vendor bar, no other section. `--dump-outputs DIR` also writes the C of the last timed step to
+DIR/sgemm_c.npy (float32; the operands are seeded, so two builds run with the same arguments can be compared output
+for output; an 8192^2 C is written as a fixed seeded sample of its elements, dump_output). Everything below the
+sgemm timing itself (the checks, the vendor bars, the x6 extra, the other sections, the N > 1 attribution) runs
+under `--full`, and `--sections` / `--inject-fault` need it.
 
 One process per GPU over RCCL/xGMI. `bench.py --gpus N` with N > 1 and no launcher environment (no WORLD_SIZE)
 starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself as a child process, before anything
@@ -71,6 +79,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 METRIC = "TFLOPS SGEMM 8192^2 + GB/s reduce 1e9 f32, at 1/2/4/8 MI355X"
 SECTIONS = ("sgemm", "reduce", "scan", "axpy", "stencil", "spmv")
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes written over all ranks
+DUMP_SEED = 20240  # --dump-outputs: seed of the element sample of an output larger than the budget
 
 
 def parse(argv=None):
@@ -107,7 +117,20 @@ def parse(argv=None):
     ap.add_argument("--inject-fault", default=None, metavar="SECTION:RANK:KIND",
                     help="test hook: KIND perturb (corrupt that rank's timed output), raise (raise in its check) or "
                          "raise-early (raise after its set-up, before the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="every section with its checks and vendor bars; without it only the headline SGEMM is set up, "
+                         "warmed up and timed (no check, no vendor bar, no other section)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the headline SGEMM's C of the last timed step to "
+                         "DIR/sgemm_c.npy (DIR/sgemm_c_rank<r>.npy at N > 1), float32; a C larger than the budget "
+                         f"({DUMP_BYTES >> 20} MiB over all ranks) is written as a fixed seeded sample of its elements")
     a = ap.parse_args(argv)
+    if not a.full:
+        for flag, given in (("--sections", a.sections != ",".join(SECTIONS)), ("--inject-fault", a.inject_fault)):
+            if given:
+                ap.error(f"{flag} needs --full (a plain run times the headline SGEMM only)")
+    elif a.dump_outputs and "sgemm" not in a.sections.split(","):
+        ap.error("--dump-outputs writes the headline SGEMM's output: sgemm must be among --sections")
     if a.small:
         a.size, a.reduce_n, a.stencil_n, a.spmv_rows, a.spmv_nnz = 256, 1e5, 256, 2e4, 2e5
     return a
@@ -348,6 +371,21 @@ def attribute_comm(ctx, chk: Checks, out: dict, prefix: str, full_ms: float, dev
     chk.info(f"{prefix}_bytes_exchanged_per_step_total", b, "sum")
 
 
+def dump_output(dirname: str, name: str, t: torch.Tensor, ctx) -> None:
+    """--dump-outputs: tensor t as DIR/<name>.npy (float32; one file per rank at N > 1). Within the byte budget the
+    whole tensor in its own shape; above it the elements at DUMP_BYTES / 4 / N flat indices drawn once from a CPU
+    generator seeded with DUMP_SEED (the same indices in every run of the same shape)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // 4 // ctx.world
+    if t.numel() > budget:
+        idx = torch.randint(t.numel(), (budget,), generator=torch.Generator().manual_seed(DUMP_SEED))
+        t = t.reshape(-1)[idx.to(t.device)]
+    fname = f"{name}.npy" if ctx.world == 1 else f"{name}_rank{ctx.rank}.npy"
+    np.save(os.path.join(dirname, fname), t.detach().float().cpu().numpy())
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
@@ -380,7 +418,12 @@ def main(argv=None):
         native_ops()  # the HIP extension must load: no silent fallback on a GPU box
         if ctx.backend == "nccl" and world > torch.cuda.device_count():
             raise SystemExit(f"[bench] {world} RCCL ranks but {torch.cuda.device_count()} GPU(s) visible")
-    sections = [s for s in args.sections.split(",") if s]
+    full = args.full
+    # a plain run (no --full) does what the headline figure needs and nothing else: the SGEMM set up, warmed up and
+    # timed (then dumped with --dump-outputs); checks, vendor bars, the x6 extra and every other section are --full's
+    sections = [s for s in args.sections.split(",") if s] if full else ["sgemm"]
+    if not full:
+        args.no_ref = args.no_x6 = True
     K, Wm = args.steps, args.warmup
     SETTLE = args.settle_ms
     LIM = W.REL_ERR_LIMIT
@@ -406,6 +449,11 @@ def main(argv=None):
         head["tflops"], head["ms"] = rep["value"], rep["ms_per_step"]
         out["sgemm_tflops_per_gpu"] = _r(rep["value"] / world, 3)
         device_times(chk, "sgemm", ms, hms)
+        if args.dump_outputs:  # what the last timed step left in C, before anything else touches it
+            dump_output(args.dump_outputs, "sgemm_c", g.c, ctx)
+        if not full:
+            log(f"sgemm {head['tflops']:.1f} TFLOPS")
+            return
         if not args.no_ref and dev.type == "cuda":
             # the vendor library timed exactly like our kernel (same warm-up and step count), into its own buffer:
             # g.c keeps the output of our timed steps for the check
@@ -628,7 +676,7 @@ def main(argv=None):
         t_ar = timed(ctx, lambda: dist.all_reduce(v), kr, 1)
         out["allreduce_256MiB_busbw_gbps"] = _r(v.numel() * 4 * 2 * (world - 1) / world * kr / t_ar / 1e9, 1)
 
-    if ctx.distributed and dev.type == "cuda" and ctx.backend == "nccl":
+    if full and ctx.distributed and dev.type == "cuda" and ctx.backend == "nccl":
         runner.run("allreduce", allreduce)
     if ctx.distributed:
         import torch.distributed as dist
@@ -642,7 +690,8 @@ def main(argv=None):
     rc = 1 if runner.failed else 0
     if rank == 0:
         # BASELINE.json publishes no number ("published": {}), so vs_baseline stays null
-        out["checks_passed"] = not runner.failed
+        if full:  # (a plain run checks nothing: no verdict in its line)
+            out["checks_passed"] = not runner.failed
         fields = dict(
             metric=METRIC, value=_r(head["tflops"], 3), unit="TFLOPS", n_gpus=world, steps=K, warmup=Wm,
             ms_per_step=_r(head["ms"]), higher_is_better=True, scaling="weak", baseline=None, dtype="fp32",
@@ -654,7 +703,7 @@ def main(argv=None):
                 "seq_len": None,
                 "parallelism": f"dp{world}",
             },
-            device=dev.type, settle_ms_before_warmup=SETTLE if dev.type == "cuda" else 0, **out)
+            device=dev.type, settle_ms_before_warmup=SETTLE if dev.type == "cuda" else 0, full=full, **out)
         try:
             line = bench_line(partial="sgemm" not in sections or "sgemm" in runner.failed, **fields)
         except ValueError as e:  # still print what was measured (with the reason), then fail the run after finalize

@@ -22,7 +22,7 @@ def _bench(nproc, *extra, timeout=240, self_launch=False):
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py")]
-    cmd += ["--gpus", str(nproc), *extra]
+    cmd += ["--gpus", str(nproc), "--full", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=cli_env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -66,8 +66,8 @@ def test_bench_more_gpus_than_visible_is_refused(gpu):
 def test_bench_wrong_result_fails_on_the_gpu(gpu):
     """A perturbed timed SGEMM C (one element; the old 8-row sample would have missed it) fails the full fp64 check:
     the line prints with sgemm_check_failed and the run exits 1."""
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "1", "--warmup", "0", "--size", "1024", "--no-ref",
-           "--sections", "sgemm", "--inject-fault", "sgemm:0:perturb"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--size", "1024",
+           "--no-ref", "--sections", "sgemm", "--inject-fault", "sgemm:0:perturb"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=120, env=cli_env())
     assert r.returncode == 1, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -494,7 +494,7 @@ def test_bench_rehearsal_gloo_world2():
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--small", "--device", "cpu"]
+           "--warmup", "1", "--small", "--device", "cpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=cli_env(OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -519,7 +519,7 @@ def test_bench_failed_section_is_reported_and_fails_the_run():
 
     from conftest import ROOT, cli_env
 
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--small", "--device", "cpu", "--steps", "1",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--small", "--device", "cpu", "--steps", "1",
                         "--warmup", "0", "--sections", "stencil,spmv", "--stencil-fuse", "99"],
                        capture_output=True, text=True, timeout=300, env=cli_env(OMP_NUM_THREADS="2"))
     assert r.returncode == 1, r.stderr[-3000:]
@@ -532,14 +532,14 @@ def test_bench_failed_section_is_reported_and_fails_the_run():
 
 
 def _bench_cpu(*extra, timeout=600):
-    """bench.py on the CPU WITHOUT a launcher (--gpus N > 1 makes it start torch.distributed.run itself)."""
+    """bench.py --full on the CPU WITHOUT a launcher (--gpus N > 1 makes it start torch.distributed.run itself)."""
     import json
     import subprocess
     import sys
 
     from conftest import ROOT, cli_env
 
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--small", "--device", "cpu", *extra],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--small", "--device", "cpu", *extra],
                        capture_output=True, text=True, timeout=timeout, env=cli_env(OMP_NUM_THREADS="1"))
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     return r, (json.loads(lines[0]) if len(lines) == 1 else None), len(lines)
@@ -659,8 +659,8 @@ def test_bench_under_launcher_without_gpus_flag():
     from parallel_c_programs_amd.parallel import free_port
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
-           "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py"), "--small", "--device", "cpu",
-           "--steps", "1", "--warmup", "0", "--sections", "reduce"]
+           "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py"), "--full", "--small", "--device",
+           "cpu", "--steps", "1", "--warmup", "0", "--sections", "reduce"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=cli_env(OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
