@@ -78,7 +78,7 @@ int pcmx_scan_f32(const float* x, float* out, long long n, int exclusive, const 
 int pcmx_scan_f32_rows(const float* x, float* out, long long n, int exclusive, const float* init_dev, void* workspace,
                        unsigned* err_flag, int rows, hipStream_t s);
 /* schedule A/B entry (csrc/kernels/scan.hip): 0 persistent R16xW8, 1 persistent R8xW16, 2 parked-tile R16xW8,
- * 3 parked-tile R8xW16, 4 parked-tile R16xW8 with early polls (pcmx_scan_f32) */
+ * 3 parked-tile R8xW16, 4 parked-tile R16xW8 with early polls (pcmx_scan_f32); any other variant: PCMX_ERR_ARG */
 int pcmx_scan_f32_variant(const float* x, float* out, long long n, int exclusive, const float* init_dev,
                           void* workspace, unsigned* err_flag, int variant, hipStream_t s);
 /* synchronises s; PCMX_ERR_TIMEOUT if the last scan on this workspace gave up a look-back, else 0 */
@@ -171,7 +171,8 @@ int pcmx_stencil5xT_bf16_spans(const void* u, void* out, int rows, int cols, int
                                int r1a, int r0b, int r1b, long long global_row0, long long global_rows, float k,
                                hipStream_t s);
 /* the same with an explicit launch shape of this launch (0 = production rule; bits 0-7 columns per lane 4 / 8, 8-15 rows
- * per wave, 16-23 prefetch ring depth 3 / 6 / 9): the lab sweeps, no state kept in the library */
+ * per wave, 16-23 prefetch ring depth 3 / 6 / 9; bits 24 and above must be 0, else -1): the lab sweeps, no state kept
+ * in the library */
 int pcmx_stencil5xT_bf16_spans_shape(const void* u, void* out, int rows, int cols, int ld, int halo, int steps, int r0a,
                                      int r1a, int r0b, int r1b, long long global_row0, long long global_rows, float k,
                                      int shape, hipStream_t s);

@@ -80,22 +80,39 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ in, long lon
     }
 }
 
-// Branch-free form (round 6 lab): one buffer descriptor per tile whose range ends at n, so the tail of the last tile
-// needs no branch. A raw buffer load checks its range per dword: the dwords past the end read as 0 (probed on the
-// MI355X, scripts/buffer_oob_probe.hip). Loads carry the nontemporal bit like load_tile's.
-template <int R, int W>
-__device__ __forceinline__ void load_tile_rs(const float* __restrict__ in, long long n, long long tile, f32x4 (&v)[R]) {
-    const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-    const long long t0 = tile * Tile<R, W>::kElems;
-    const long long rem = n - t0;
-    // a tile past the end (the schedule's "next" after the last tile) gets an empty range: every load reads 0 and
-    // touches no memory, so the caller issues it without a branch
-    const int bytes = (int)((rem <= 0 ? 0 : rem < Tile<R, W>::kElems ? rem : (long long)Tile<R, W>::kElems) * 4);
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in + t0), 0, bytes, 0x00020000);
-    const int off = (wave * Tile<R, W>::kWaveItems + lane * 4) * 4;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-        v[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + r * 1024, 0, 2));
+// ---- pieces shared by the persistent and the parked schedule. (The in-wave row scan and the block aggregate loop stay
+// written out in both: as helpers they changed the generated code, profiles/r7_cleanup/README.md.)
+// One output row from its scanned row v and the prefix b of everything before the row's first element.
+__device__ __forceinline__ f32x4 output_row(const f32x4& v, float b, int exclusive) {
+    f32x4 o;
+    if (exclusive) {
+        o.x = b;
+        o.y = b + v.x;
+        o.z = b + v.y;
+        o.w = b + v.z;
+    } else {
+        o = v + b;
+    }
+    return o;
+}
+
+// Stores a row at element e; `full` (block-uniform) = the whole tile lies below n, otherwise the tail is clipped.
+__device__ __forceinline__ void store_row(float* out, long long n, long long e, bool full, f32x4 o) {
+    if (full || e + 3 < n) {
+        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(out + e));
+    } else {
+        if (e < n) out[e] = o.x;
+        if (e + 1 < n) out[e + 1] = o.y;
+        if (e + 2 < n) out[e + 2] = o.z;
+    }
+}
+
+// A look-back that ran out of spins: marks the result invalid in the workspace and in the caller's sticky word.
+__device__ __forceinline__ void report_timeout(ScanWs* ws, unsigned* err_flag) {
+    if (pcmx::lane_id() == 0) {
+        atomicExch(&ws->timeout, 1u);
+        if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 // Scans tile `tile` held in v, publishes it, issues the loads of `next` into vn, looks back, stores.
@@ -172,10 +189,7 @@ __device__ __forceinline__ void finish_tile(const float* __restrict__ in, float*
                     continue;
                 }
                 if (++spins > kSpinLimit) {  // bounded spin: report (workspace + sticky caller word) and fall through
-                    if (lane == 0) {
-                        atomicExch(&ws->timeout, 1u);
-                        if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
+                    report_timeout(ws, err_flag);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(1);
@@ -195,24 +209,8 @@ __device__ __forceinline__ void finish_tile(const float* __restrict__ in, float*
     const bool full = (tile + 1) * Tile<R, W>::kElems <= n;  // block-uniform
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const float b = off + lane_excl[r];
-        f32x4 o;
-        if (exclusive) {
-            o.x = b;
-            o.y = b + v[r].x;
-            o.z = b + v[r].y;
-            o.w = b + v[r].z;
-        } else {
-            o = v[r] + b;
-        }
-        const long long e = base + r * 256 + lane * 4;
-        if (full || e + 3 < n) {
-            __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(out + e));
-        } else {
-            if (e < n) out[e] = o.x;
-            if (e + 1 < n) out[e + 1] = o.y;
-            if (e + 2 < n) out[e + 2] = o.z;
-        }
+        const f32x4 o = output_row(v[r], off + lane_excl[r], exclusive);
+        store_row(out, n, base + r * 256 + lane * 4, full, o);
     }
 }
 
@@ -313,10 +311,7 @@ __device__ __forceinline__ float parked_lookback(long long tile, ScanWs* ws, uns
         if (done) break;
         if (stall) {
             if (++spins > kSpinLimit) {  // bounded spin, reported as in the persistent schedule
-                if (lane == 0) {
-                    atomicExch(&ws->timeout, 1u);
-                    if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+                report_timeout(ws, err_flag);
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -351,24 +346,15 @@ __device__ __forceinline__ void parked_flush(float* __restrict__ out, long long 
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const f32x4 o = park[(wave * R + r) * kWave + lane] + off;
-        const long long e = base + r * 256 + lane * 4;
-        if (full || e + 3 < n) {
-            __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(out + e));
-        } else {
-            if (e < n) out[e] = o.x;
-            if (e + 1 < n) out[e + 1] = o.y;
-            if (e + 2 < n) out[e + 2] = o.z;
-        }
+        store_row(out, n, base + r * 256 + lane * 4, full, o);
     }
 }
 
 // One iteration: scan `cur` (in v) and publish its aggregate, issue the loads of `next` into vn, take a ticket,
 // flush `prev` from the park buffer, park `cur`. Returns cur's aggregate (thread 0 needs it one iteration later).
-// kLoadAt (round 6 lab): where the loads of `next` go out. 0 (production): after cur's scan and publish. 1: at the TOP
-// of the iteration (vn is free there: its last tile was parked an iteration ago), before wave 0's early polls. 2:
-// right AFTER the early polls, before the scan. vmcnt retires in issue order, so under 1 the look-back's wait for its
-// polls also waits for the whole next tile; 2 keeps the polls ahead of the loads.
-template <int R, int W, bool kEarly, int kLoadAt = 0, bool kRs = false>
+// The loads of `next` go out after cur's scan and publish, not earlier: vmcnt retires in issue order, so loads issued
+// before the polls delay the look-back (earlier placements measured and rejected: profiles/r6_scan/).
+template <int R, int W, bool kEarly>
 __device__ __forceinline__ float parked_step(const float* __restrict__ in, float* __restrict__ out, long long n,
                                              long long cur, f32x4 (&v)[R], long long next, f32x4 (&vn)[R],
                                              long long prev, float agg_prev, long long ntiles, int exclusive, float init,
@@ -377,21 +363,9 @@ __device__ __forceinline__ float parked_step(const float* __restrict__ in, float
     unsigned long long* status = reinterpret_cast<unsigned long long*>(ws + 1);
     const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
     // kEarly: wave 0 sends prev's first round of polls BEFORE this tile's scan, so their round trip overlaps it
-    if constexpr (kLoadAt == 1) {
-        if constexpr (kRs)
-            load_tile_rs<R, W>(in, n, next, vn);  // branch-free (an empty range past the last tile)
-        else if (next < ntiles)
-            load_tile<R, W>(in, n, next, vn);
-    }
     ParkPoll sv;
     const bool polled = kEarly && wave == 0 && prev > 0;
     if (polled) parked_poll(prev, prev - 1, ws, sv);
-    if constexpr (kLoadAt == 2) {
-        if constexpr (kRs)
-            load_tile_rs<R, W>(in, n, next, vn);  // branch-free (an empty range past the last tile)
-        else if (next < ntiles)
-            load_tile<R, W>(in, n, next, vn);
-    }
     float carry = 0.f;
     float lane_excl[R];
 #pragma unroll
@@ -417,32 +391,16 @@ __device__ __forceinline__ float parked_step(const float* __restrict__ in, float
     if (threadIdx.x == 0)
         __hip_atomic_store(&status[cur], pack(cur == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
-    if constexpr (kLoadAt == 0) {
-        if constexpr (kRs)
-            load_tile_rs<R, W>(in, n, next, vn);  // branch-free (an empty range past the last tile)
-        else if (next < ntiles)
-            load_tile<R, W>(in, n, next, vn);
-    }
+    if (next < ntiles) load_tile<R, W>(in, n, next, vn);
     const unsigned ticket = threadIdx.x == 0 ? atomicAdd(&ws->ticket, 1u) : 0u;
     parked_flush<R, W>(out, n, prev, agg_prev, init, ws, err_flag, park, s_prefix, s_next, ticket, sv, polled);
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const float b = wexcl + lane_excl[r];
-        f32x4 o;
-        if (exclusive) {
-            o.x = b;
-            o.y = b + v[r].x;
-            o.z = b + v[r].y;
-            o.w = b + v[r].z;
-        } else {
-            o = v[r] + b;
-        }
-        park[(wave * R + r) * kWave + lane] = o;
-    }
+    for (int r = 0; r < R; ++r)
+        park[(wave * R + r) * kWave + lane] = output_row(v[r], wexcl + lane_excl[r], exclusive);
     return agg;
 }
 
-template <int R, int W, bool kEarly, int kLoadAt = 0, bool kRs = false>
+template <int R, int W, bool kEarly>
 __global__ __launch_bounds__(W * kWave) void scan_parked_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                                 long long n, long long ntiles, int exclusive,
                                                                 const float* init_dev, ScanWs* ws, unsigned* err_flag) {
@@ -460,20 +418,17 @@ __global__ __launch_bounds__(W * kWave) void scan_parked_kernel(const float* __r
     long long ta = s_tile[0], tb = s_tile[1], prev = -1;
     if (ta >= ntiles) return;
     float agg_prev = 0.f;
-    if constexpr (kRs)
-        load_tile_rs<R, W>(in, n, ta, va);
-    else
-        load_tile<R, W>(in, n, ta, va);
+    load_tile<R, W>(in, n, ta, va);
     // unrolled by two so both register buffers are statically named; every exit is block-uniform and ends with
     // the flush of the last parked tile
     while (true) {
-        agg_prev = parked_step<R, W, kEarly, kLoadAt, kRs>(in, out, n, ta, va, tb, vb, prev, agg_prev, ntiles, exclusive, init, ws, err_flag,
-                                     park, s_wave_tot, &s_prefix, &s_tile[0]);
+        agg_prev = parked_step<R, W, kEarly>(in, out, n, ta, va, tb, vb, prev, agg_prev, ntiles, exclusive, init, ws, err_flag,
+                                             park, s_wave_tot, &s_prefix, &s_tile[0]);
         prev = ta;
         ta = s_tile[0];
         if (tb >= ntiles) break;
-        agg_prev = parked_step<R, W, kEarly, kLoadAt, kRs>(in, out, n, tb, vb, ta, va, prev, agg_prev, ntiles, exclusive, init, ws, err_flag,
-                                     park, s_wave_tot, &s_prefix, &s_tile[0]);
+        agg_prev = parked_step<R, W, kEarly>(in, out, n, tb, vb, ta, va, prev, agg_prev, ntiles, exclusive, init, ws, err_flag,
+                                             park, s_wave_tot, &s_prefix, &s_tile[0]);
         prev = tb;
         tb = s_tile[0];
         if (ta >= ntiles) break;
@@ -500,7 +455,7 @@ extern "C" long long pcmx_scan_workspace_bytes(long long n) { return (long long)
 extern "C" int pcmx_scan_f32_variant(const float* x, float* out, long long n, int exclusive, const float* init_dev,
                                      void* workspace, unsigned* err_flag, int variant, hipStream_t s) {
     if (n <= 0) return 0;
-    if (variant < 0 || variant > 8) return PCMX_ERR_ARG;
+    if (variant < 0 || variant > 4) return PCMX_ERR_ARG;
     if ((((uintptr_t)x) & 15u) || (((uintptr_t)out) & 15u) || !workspace) return PCMX_ERR_ARG;
     const long long tiles = num_tiles(n);
     if (tiles > 0x7fffffffLL) return PCMX_ERR_ARG;
@@ -512,10 +467,6 @@ extern "C" int pcmx_scan_f32_variant(const float* x, float* out, long long n, in
         case 1: scan_persistent_kernel<8, 16><<<grid, 16 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
         case 2: scan_parked_kernel<16, 8, false><<<grid, 8 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
         case 3: scan_parked_kernel<8, 16, false><<<grid, 16 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
-        case 5: scan_parked_kernel<16, 8, true, 1><<<grid, 8 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
-        case 6: scan_parked_kernel<16, 8, true, 2><<<grid, 8 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
-        case 7: scan_parked_kernel<16, 8, true, 0, true><<<grid, 8 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
-        case 8: scan_parked_kernel<16, 8, true, 2, true><<<grid, 8 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
         default: scan_parked_kernel<16, 8, true><<<grid, 8 * kWave, 0, s>>>(x, out, n, tiles, exclusive, init_dev, ws, err_flag); break;
     }
     return (int)hipGetLastError();

@@ -15,8 +15,7 @@ Run: python scripts/stencil_rank_lab.py [fuse ...]
 Env: STENCIL_LAB_WORLDS=8 (subset of 1,2,4,8), STENCIL_LAB_RPW=0,18 (rows per wave forced on the non-edge launches
 as an explicit launch shape of each call, ops.stencil.launch_shape; 0 = production rule; one line per value, all in one
 process for an A/B); STENCIL_LAB_DEEP=2,3,4 (halo depths m); STENCIL_LAB_ONLY=full (subset of full, split3, split2, split2c); STENCIL_LAB_AHEAD=3 / 6 / 9 (prefetch ring
-of the forced shapes); STENCIL_LAB_CPL=4 / 8 (columns per lane of the forced shapes); STENCIL_LAB_PAIRED=0,1 (round 6:
-paired waves off / on for the non-edge launches, one line per value); STENCIL_LAB_RCCL=1 (round 6:
+of the forced shapes); STENCIL_LAB_CPL=4 / 8 (columns per lane of the forced shapes); STENCIL_LAB_RCCL=1 (round 6:
 each deep-halo variant also runs WITH its exchange: the real halo bytes, 2 x mT rows, through the native exchange on a
 world-1 RCCL communicator, posted before the interior launch and waited before the edge launch as StencilSlab.step
 does; printed as deepM+x); STENCIL_LAB_DEEP_BUFS=2 (round 6 default: the deep-halo phases ping-pong between two
@@ -63,14 +62,12 @@ def main():
     g = torch.Generator(device=dev).manual_seed(1)
     worlds = [int(w) for w in os.environ.get("STENCIL_LAB_WORLDS", "1,2,4,8").split(",")]
     rpws = [int(r) for r in os.environ.get("STENCIL_LAB_RPW", "0").split(",")]
-    pairs = [{"": None, "1": True, "0": False}[p] for p in os.environ.get("STENCIL_LAB_PAIRED", "").split(",")]
     # STENCIL_LAB_EDGE=cpl:rpw[:ahead] (round 6): an explicit shape for the deep-halo step's edge launch (the two rank-edge
     # bands, <= 64 rows: production 4 columns per lane x 2-row waves)
     edge_spec = [int(v) for v in os.environ.get("STENCIL_LAB_EDGE", "0:0").split(":")] + [0]
     edge_shape = launch_shape(edge_spec[0], edge_spec[1], edge_spec[2]) if any(edge_spec) else 0
-    for T, world, rpw, paired in [(T, w, r, p) for T in fuses for w in worlds for r in rpws for p in pairs]:
-        shape = launch_shape(int(os.environ.get("STENCIL_LAB_CPL", "0")), rpw, int(os.environ.get("STENCIL_LAB_AHEAD", "0")),
-                             paired)
+    for T, world, rpw in [(T, w, r) for T in fuses for w in worlds for r in rpws]:
+        shape = launch_shape(int(os.environ.get("STENCIL_LAB_CPL", "0")), rpw, int(os.environ.get("STENCIL_LAB_AHEAD", "0")))
 
         def step(*a, shape=shape, **kw):  # the non-edge launches take the forced rows per wave
             return ops.stencil5_fused_step_(*a, shape=shape, **kw)
@@ -162,7 +159,7 @@ def main():
                 res[name] = (timed(fn), same)
             line = " ".join(f"{k} {ms:.4f} ms {rows * N * T / ms / 1e6:7.0f} GLUP/s{'' if ok else ' MISMATCH'}"
                             for k, (ms, ok) in res.items())
-            tag = (f" rpw={rpw}" if rpw else "") + ("" if paired is None else f" paired={int(paired)}")
+            tag = f" rpw={rpw}" if rpw else ""
             print(f"fuse={T} N={world} rows={rows:5d}{tag}  {line}", flush=True)
             del u, ref, out, deeps
             torch.cuda.empty_cache()

@@ -284,12 +284,11 @@ def test_stencil_fused_every_lane_geometry(gpu, shape, steps):
 
 
 @pytest.mark.parametrize("steps", [6])
-def test_stencil_paired_waves_bit_identical(gpu, steps):
-    """Paired waves (round 6, stencil5xT2p_kernel: two vertically adjacent waves march down / up and trade their
-    common trapezoid through LDS; a measured, not adopted lab shape) give the bits of the unpaired kernel and of the CPU oracle: a rank's slab inside a
-    larger grid (no Dirichlet row in reach, so the paired path runs), rows per wave from T up, last blocks whose lower
-    wave has 1 row, several rows, or none, a two-span launch, and a slab touching the global edge (the unpaired
-    fall-back of such blocks)."""
+def test_stencil_short_slab_shapes_bit_exact(gpu, steps):
+    """The 4-column kernel on short slabs gives the bits of the CPU oracle: a rank's slab deep inside a larger grid
+    (halo = steps, no Dirichlet row in reach), rows per wave from T up, last blocks whose lower wave has 1 row, several
+    rows, or none, a slab touching the global edge, and a two-span launch. A shape word with bits above the prefetch
+    field set (the removed paired-wave lab shapes) is refused."""
     from parallel_c_programs_amd.ops.stencil import launch_shape
 
     cols = 1032
@@ -301,13 +300,11 @@ def test_stencil_paired_waves_bit_identical(gpu, steps):
                 ref = u.clone()
                 ops.stencil5_fused_step_(u, ref, row0, grows, halo=steps, steps=steps)  # CPU oracle
                 a = u.to(gpu)
-                for paired in (True, False):
-                    b = torch.zeros_like(a)
-                    ops.stencil5_fused_step_(a, b, row0, grows, halo=steps, steps=steps,
-                                             shape=launch_shape(4, rpw, 0, paired))
-                    got = b.cpu()[steps:-steps].view(torch.int16)
-                    assert torch.equal(got, ref[steps:-steps].view(torch.int16)), (rpw, rows, row0, paired)
-            # two spans in one launch (the distributed step's edge bands, here wide enough for pairs)
+                b = torch.zeros_like(a)
+                ops.stencil5_fused_step_(a, b, row0, grows, halo=steps, steps=steps, shape=launch_shape(4, rpw, 0))
+                got = b.cpu()[steps:-steps].view(torch.int16)
+                assert torch.equal(got, ref[steps:-steps].view(torch.int16)), (rpw, rows, row0)
+            # two spans in one launch (the distributed step's edge bands, here several blocks each)
             row0, grows = 5000, 100000
             ref = u.clone()
             ops.stencil5_fused_step_(u, ref, row0, grows, halo=steps, steps=steps)
@@ -315,11 +312,12 @@ def test_stencil_paired_waves_bit_identical(gpu, steps):
             b = a.clone()
             mid = rows // 2
             ops.stencil5_fused_spans_(a, b, ((0, mid - 7), (mid + 5, rows)), row0, grows, halo=steps, steps=steps,
-                                      shape=launch_shape(4, rpw, 0, True))
+                                      shape=launch_shape(4, rpw, 0))
             ops.stencil5_fused_step_(a, b, row0, grows, halo=steps, steps=steps, row_range=(mid - 7, mid + 5))
             assert torch.equal(b.cpu()[steps:-steps].view(torch.int16), ref[steps:-steps].view(torch.int16)), (rpw, rows)
-    with pytest.raises(RuntimeError):  # paired waves exist for T = 6 with 4 columns per lane only (a lab shape)
-        ops.stencil5_fused_step_(a, b, 5000, 100000, halo=steps, steps=steps, shape=launch_shape(8, 24, 0, True))
+    for high in (1 << 24, 2 << 24):  # the removed paired-wave bits: refused, not ignored
+        with pytest.raises(RuntimeError):
+            ops.stencil5_fused_step_(a, b, 5000, 100000, halo=steps, steps=steps, shape=launch_shape(4, 24) | high)
 
 
 @pytest.mark.parametrize("steps", [2, 4, 6])
