@@ -84,6 +84,26 @@ int pcmx_scan_f32_variant(const float* x, float* out, long long n, int exclusive
 /* synchronises s; PCMX_ERR_TIMEOUT if the last scan on this workspace gave up a look-back, else 0 */
 int pcmx_scan_check(const void* workspace, hipStream_t s);
 
+/* ---------------------------------------------------------------- stream compaction (select / nonzero) */
+/* Keeps the selected elements of a length-n stream in input order and stores how many were kept to *count_dev
+ * (int64, device memory) without a host sync: one pass on the scan's decoupled look-back, carrying the exact u32
+ * kept count per tile (csrc/kernels/select.hip). out needs room for n elements (count is not known on the host);
+ * elements of out at or past the count are not written. x and out 16-B aligned, mask 4-B aligned, n < 2^31 (else
+ * PCMX_ERR_ARG); n <= 0 stores count 0 and returns 0. out must not overlap x or mask. A look-back that gives up is
+ * reported as for pcmx_scan_f32: in the workspace (pcmx_scan_check reads a select workspace too) and in *err_flag. */
+enum { PCMX_CMP_GT = 0, PCMX_CMP_GE = 1, PCMX_CMP_LT = 2, PCMX_CMP_LE = 3, PCMX_CMP_EQ = 4, PCMX_CMP_NE = 5 };
+long long pcmx_select_workspace_bytes(long long n);
+/* out[j] = x[i] for the j-th i with mask[i] != 0; x is any 4-byte payload moved as bits (f32 NaN payloads survive) */
+int pcmx_select_b32(const void* x, const unsigned char* mask, void* out, long long n, long long* count_dev,
+                    void* workspace, unsigned* err_flag, hipStream_t s);
+/* out_idx[j] = i (int32) for the j-th i with mask[i] != 0: a flattened nonzero */
+int pcmx_select_index(const unsigned char* mask, int* out_idx, long long n, long long* count_dev, void* workspace,
+                      unsigned* err_flag, hipStream_t s);
+/* keeps x[i] OP threshold (PCMX_CMP_*, IEEE: NaN is kept only by NE); writes the kept f32 values, or with
+ * want_index != 0 their int32 indices; no mask is materialised */
+int pcmx_select_if_f32(const float* x, int op, float threshold, void* out_or_idx, int want_index, long long n,
+                       long long* count_dev, void* workspace, unsigned* err_flag, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

@@ -224,6 +224,107 @@ at::Tensor scan(const at::Tensor& x, bool exclusive, const c10::optional<at::Ten
     return scan_out(xc, out, exclusive, init).view(x.sizes());
 }
 
+// ---------------------------------------------------------------- stream compaction (select / nonzero)
+// The three select ops return (out, count): out has room for x.numel() elements (the count is not known on the host),
+// count is a 0-d int64 tensor on the device; nothing synchronises. They share the scan's per-(device, stream) sticky
+// error word, so scan_check() covers a select whose look-back gave up.
+bool overlaps(const at::Tensor& a, const at::Tensor& b) {
+    const auto a0 = reinterpret_cast<uintptr_t>(a.data_ptr()), b0 = reinterpret_cast<uintptr_t>(b.data_ptr());
+    const uintptr_t ab = (uintptr_t)a.numel() * a.element_size(), bb = (uintptr_t)b.numel() * b.element_size();
+    return a0 < b0 + bb && b0 < a0 + ab;
+}
+
+// The flag bytes of a bool / uint8 mask, contiguous and 4-B aligned.
+at::Tensor mask_bytes(const at::Tensor& mask, int64_t n, const char* what) {
+    TORCH_CHECK(mask.is_cuda(), what, ": mask must be a GPU tensor");
+    TORCH_CHECK(mask.scalar_type() == at::kBool || mask.scalar_type() == at::kByte, what, ": mask has dtype ",
+                mask.scalar_type(), ", expected bool or uint8");
+    TORCH_CHECK(mask.numel() == n, what, ": mask has ", mask.numel(), " elements, expected ", n);
+    at::Tensor m = mask.contiguous().view(-1);
+    if (m.scalar_type() == at::kBool) m = m.view(at::kByte);
+    if (reinterpret_cast<uintptr_t>(m.data_ptr()) & 3u) m = m.clone();
+    return m;
+}
+
+// The tensor the kernel writes (16-B aligned): `out` itself, a copy of it (so what lies past the count survives the
+// copy back) when it is misaligned, or a fresh one of n elements.
+at::Tensor select_dest(const c10::optional<at::Tensor>& out, const at::Tensor& like, at::ScalarType dt, int64_t n,
+                       const char* what) {
+    if (!(out.has_value() && out->defined())) return at::empty({n}, like.options().dtype(dt));
+    check_gpu(*out, "out", dt);
+    TORCH_CHECK(out->device() == like.device() && out->is_contiguous() && out->numel() >= n, what,
+                ": out must be contiguous, on the input's device, with room for all ", n, " elements");
+    return (reinterpret_cast<uintptr_t>(out->data_ptr()) & 15u) ? out->clone() : *out;
+}
+
+std::tuple<at::Tensor, at::Tensor> select_finish(const c10::optional<at::Tensor>& out, const at::Tensor& dest,
+                                                 const at::Tensor& count) {
+    if (out.has_value() && out->defined()) {
+        if (!dest.is_same(*out)) out->copy_(dest);
+        return {*out, count};
+    }
+    return {dest, count};
+}
+
+std::tuple<at::Tensor, at::Tensor> select_b32(const at::Tensor& x, const at::Tensor& mask, const c10::optional<at::Tensor>& out) {
+    TORCH_CHECK(x.is_cuda(), "select: x must be a GPU tensor");
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kInt, "select: x has dtype ", x.scalar_type(),
+                ", expected float32 or int32");
+    TORCH_CHECK(mask.device() == x.device(), "select: mask must be on x's device");
+    const at::DeviceGuard g(x.device());
+    hipStream_t stream = cur_stream(x);
+    unsigned* err_dev = scan_err_word(x.device().index(), stream).dev;
+    raise_pending_scan_error(x.device().index(), stream);
+    const int64_t n = x.numel();
+    at::Tensor xc = aligned_contig(x).view(-1), mc = mask_bytes(mask, n, "select");
+    at::Tensor dest = select_dest(out, x, x.scalar_type(), n, "select");
+    if (overlaps(xc, dest)) xc = xc.clone();
+    if (overlaps(mc, dest)) mc = mc.clone();
+    at::Tensor count = at::empty({}, x.options().dtype(at::kLong));
+    auto ws = workspace(x, pcmx_select_workspace_bytes(n));
+    check_rc(pcmx_select_b32(xc.data_ptr(), mc.data_ptr<uint8_t>(), dest.data_ptr(), n, (long long*)count.data_ptr<int64_t>(),
+                             ws.data_ptr(), err_dev, stream),
+             "select");
+    return select_finish(out, dest, count);
+}
+
+std::tuple<at::Tensor, at::Tensor> select_index(const at::Tensor& mask, const c10::optional<at::Tensor>& out) {
+    const at::DeviceGuard g(mask.device());
+    const int64_t n = mask.numel();
+    at::Tensor mc = mask_bytes(mask, n, "select_index");
+    hipStream_t stream = cur_stream(mask);
+    unsigned* err_dev = scan_err_word(mask.device().index(), stream).dev;
+    raise_pending_scan_error(mask.device().index(), stream);
+    at::Tensor dest = select_dest(out, mask, at::kInt, n, "select_index");
+    if (overlaps(mc, dest)) mc = mc.clone();
+    at::Tensor count = at::empty({}, mask.options().dtype(at::kLong));
+    auto ws = workspace(mask, pcmx_select_workspace_bytes(n));
+    check_rc(pcmx_select_index(mc.data_ptr<uint8_t>(), dest.data_ptr<int>(), n, (long long*)count.data_ptr<int64_t>(),
+                               ws.data_ptr(), err_dev, stream),
+             "select_index");
+    return select_finish(out, dest, count);
+}
+
+std::tuple<at::Tensor, at::Tensor> select_if(const at::Tensor& x, int64_t op, double threshold, bool indices,
+                                             const c10::optional<at::Tensor>& out) {
+    check_gpu(x, "x", at::kFloat);
+    TORCH_CHECK(op >= PCMX_CMP_GT && op <= PCMX_CMP_NE, "select_if: op code ", op);
+    const at::DeviceGuard g(x.device());
+    hipStream_t stream = cur_stream(x);
+    unsigned* err_dev = scan_err_word(x.device().index(), stream).dev;
+    raise_pending_scan_error(x.device().index(), stream);
+    const int64_t n = x.numel();
+    at::Tensor xc = aligned_contig(x).view(-1);
+    at::Tensor dest = select_dest(out, x, indices ? at::kInt : at::kFloat, n, "select_if");
+    if (overlaps(xc, dest)) xc = xc.clone();
+    at::Tensor count = at::empty({}, x.options().dtype(at::kLong));
+    auto ws = workspace(x, pcmx_select_workspace_bytes(n));
+    check_rc(pcmx_select_if_f32(xc.data_ptr<float>(), (int)op, (float)threshold, dest.data_ptr(), indices ? 1 : 0, n,
+                                (long long*)count.data_ptr<int64_t>(), ws.data_ptr(), err_dev, stream),
+             "select_if");
+    return select_finish(out, dest, count);
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -755,6 +856,9 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("scan(Tensor x, bool exclusive=False, Tensor? init=None) -> Tensor");
     m.def("scan_out(Tensor x, Tensor(a!) out, bool exclusive=False, Tensor? init=None) -> Tensor(a!)");
     m.def("scan_check(int device=0) -> ()", scan_check);
+    m.def("select(Tensor x, Tensor mask, Tensor(a!)? out=None) -> (Tensor, Tensor)");
+    m.def("select_index(Tensor mask, Tensor(a!)? out=None) -> (Tensor, Tensor)");
+    m.def("select_if(Tensor x, int op, float threshold, bool indices=False, Tensor(a!)? out=None) -> (Tensor, Tensor)");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -793,6 +897,9 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("dot", dot);
     m.impl("scan", scan);
     m.impl("scan_out", scan_out);
+    m.impl("select", select_b32);  // (::select is the POSIX call)
+    m.impl("select_index", select_index);
+    m.impl("select_if", select_if);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

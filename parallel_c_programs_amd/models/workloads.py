@@ -567,8 +567,80 @@ class Region2D(Workload):
         return {"region_pixels": int(reg.sum()), "matches_cpu_oracle": bool(ok), "check_passed": bool(ok)}
 
 
+class Select(Workload):
+    """Stream compaction of n f32 per GPU: keep the elements a mask (mode "mask": values, "index": their int32
+    indices) or a predicate (mode "where": x < keep, no mask) selects, in order, with the count left on the device.
+    x is uniform in [0, 1); the mask keeps element i when a seeded counter hash of i falls below the keep fraction.
+    No communication (weak scaling)."""
+
+    def __init__(self, ctx, n=1 << 28, keep=0.5, mode="mask", **_):
+        if mode not in ("mask", "index", "where"):
+            raise ValueError(f"select mode {mode!r}: mask, index or where")
+        super().__init__(ctx, {"n": int(n), "keep": float(keep), "mode": mode}, "select", "GB/s")
+        n, dev = int(n), ctx.device
+        self.mode, self.keep = mode, float(keep)
+        self.x = torch.empty(n, device=dev)
+        ops.rand_uniform_(self.x, 7000 + ctx.rank, 0.0, 1.0)
+        self.mask = None
+        if mode != "where":
+            u = ops.rand_uniform_(torch.empty(n, device=dev), 8000 + ctx.rank, 0.0, 1.0)  # the seeded counter
+            self.mask = u < self.keep
+            del u
+        self.out = torch.empty(n, device=dev, dtype=torch.float32 if mode != "index" else torch.int32)
+        self.count = None
+
+    def step(self):
+        if self.mode == "mask":
+            _, self.count = ops.compact(self.x, self.mask, out=self.out)
+        elif self.mode == "index":
+            _, self.count = ops.compact_indices(self.mask, out=self.out)
+        else:
+            _, self.count = ops.compact_where(self.x, "lt", self.keep, out=self.out)
+
+    def torch_step(self):
+        """The same selection through torch (the vendor bar; it synchronises for the size of its result)."""
+        if self.mode == "mask":
+            return self.x[self.mask]
+        if self.mode == "index":
+            return torch.nonzero(self.mask)
+        return self.x[self.x < self.keep]
+
+    def kept(self) -> int:
+        return int(self.count.item()) if self.count is not None else 0
+
+    def work_per_step(self):
+        # bytes moved: mask select reads 4n payload + n flags and writes 4k; index select reads the n flags alone;
+        # the predicate reads the payload alone
+        n, k = self.x.numel(), self.kept()
+        return float({"mask": 5 * n, "index": n, "where": 4 * n}[self.mode] + 4 * k)
+
+    def check(self, reduce: bool = True, chunk: int = 1 << 26):
+        """Every output of the timed step and the count against torch (x[mask] / nonzero / x[x < keep]), bit for bit,
+        chunk by chunk of the input; and the look-back error word of the stream. Local only."""
+        lookback_ok = True
+        if self.x.is_cuda:
+            try:
+                ops.scan_check(self.x.device)
+            except RuntimeError:
+                lookback_ok = False
+        k, n, pos, same = self.kept(), self.x.numel(), 0, True
+        for s in range(0, n, chunk):
+            xs = self.x[s:s + chunk]
+            keep = self.mask[s:s + chunk] if self.mode != "where" else xs < self.keep
+            ref = (torch.nonzero(keep).reshape(-1) + s).int() if self.mode == "index" else xs[keep]
+            m = ref.numel()
+            same = same and pos + m <= k and torch.equal(self.out[pos:pos + m].view(torch.int32), ref.view(torch.int32))
+            pos += m
+        ok = bool(same and pos == k)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+            lookback_ok = self.ctx.max_over_ranks(0.0 if lookback_ok else 1.0) == 0.0
+        return {"kept": k, "kept_torch": pos, "elements_checked": pos, "bit_exact_vs_torch": ok,
+                "lookback_ok": lookback_ok, "check_passed": ok and lookback_ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
-             "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D}
+             "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

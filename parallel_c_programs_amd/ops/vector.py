@@ -130,3 +130,95 @@ def rand_uniform_(x: torch.Tensor, seed: int = 0, lo: float = -1.0, hi: float = 
         return ops().rand_uniform_(x, int(seed), float(lo), float(hi))
     g = torch.Generator().manual_seed(int(seed))
     return x.uniform_(lo, hi, generator=g)
+
+
+# ---------------------------------------------------------------- stream compaction (select / nonzero)
+# Keep the elements a mask or a predicate selects, in input order, and report how many were kept. On the GPU this is
+# one pass on the scan's decoupled look-back carrying the exact integer kept count (csrc/kernels/select.hip); the
+# ancestor is the pixel-stack frontier of the region programs (ref 2-mpi-region-growing/region.c:493-533). The
+# compact* forms return (out, count) with count a 0-d int64 tensor on x's device and never synchronise: out has room
+# for every element and only out[:count] is written. select / select_indices cut out to the exact size (one host sync).
+CMP_CODES = {"gt": 0, "ge": 1, "lt": 2, "le": 3, "eq": 4, "ne": 5}
+_CMP_TORCH = {"gt": torch.gt, "ge": torch.ge, "lt": torch.lt, "le": torch.le, "eq": torch.eq, "ne": torch.ne}
+
+
+def _check_mask(mask: torch.Tensor, n: int | None) -> None:
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"mask must be bool or uint8, got {mask.dtype}")
+    if n is not None and mask.numel() != n:
+        raise ValueError(f"mask has {mask.numel()} elements, x has {n}")
+
+
+def _check_out(out: torch.Tensor | None, dtype: torch.dtype, n: int, like: torch.Tensor) -> None:
+    if out is None:
+        return
+    if out.dtype != dtype:
+        raise TypeError(f"out must be {dtype}, got {out.dtype}")
+    if out.device != like.device:
+        raise ValueError(f"out is on {out.device}, the input on {like.device}")
+    if out.dim() != 1 or not out.is_contiguous() or out.numel() < n:
+        raise ValueError(f"out must be 1-D, contiguous, with room for all {n} elements (the count is not known "
+                         f"before the kernel ran), got shape {tuple(out.shape)}")
+
+
+def _host_result(kept: torch.Tensor, n: int, out: torch.Tensor | None):
+    """The CPU paths' (out, count): the kept elements at the front of an n-element (or the caller's) tensor."""
+    if out is None:
+        out = kept.new_empty(n)
+    out[:kept.numel()] = kept
+    return out, torch.tensor(kept.numel(), dtype=torch.int64)
+
+
+def compact(x: torch.Tensor, mask: torch.Tensor, out: torch.Tensor | None = None):
+    """(out, count): out[j] = x.flatten()[i] for the j-th i with mask.flatten()[i] != 0, count of them as a 0-d int64
+    tensor on x's device. x float32 or int32 (moved as bits: NaN payloads survive), mask bool or uint8 of the same
+    numel (any nonzero byte keeps). out (optional, 1-D, >= x.numel() elements) is left untouched past count. Does not
+    synchronise."""
+    if x.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"x must be float32 or int32, got {x.dtype}")
+    _check_mask(mask, x.numel())
+    _check_out(out, x.dtype, x.numel(), x)
+    if x.is_cuda:
+        return tuple(ops().select(x, mask, out))
+    return _host_result(x.reshape(-1)[mask.reshape(-1) != 0], x.numel(), out)
+
+
+def select(x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """x.flatten()[mask.flatten()] as a tensor of exactly count elements (one host sync for the count)."""
+    out, count = compact(x, mask)
+    return out[:int(count.item())]
+
+
+def compact_indices(mask: torch.Tensor, out: torch.Tensor | None = None):
+    """(idx, count): the int32 flat indices of the nonzero mask elements, ascending (a flattened nonzero), and their
+    count as a 0-d int64 tensor on the mask's device. Does not synchronise."""
+    _check_mask(mask, None)
+    if mask.numel() >= 1 << 31:
+        raise ValueError("compact_indices: indices are int32, the mask must have fewer than 2^31 elements")
+    _check_out(out, torch.int32, mask.numel(), mask)
+    if mask.is_cuda:
+        return tuple(ops().select_index(mask, out))
+    return _host_result(torch.nonzero(mask.reshape(-1)).reshape(-1).int(), mask.numel(), out)
+
+
+def select_indices(mask: torch.Tensor) -> torch.Tensor:
+    """torch.nonzero(mask.flatten()).flatten().int(), exact size (one host sync for the count)."""
+    idx, count = compact_indices(mask)
+    return idx[:int(count.item())]
+
+
+def compact_where(x: torch.Tensor, op: str, threshold: float, indices: bool = False, out: torch.Tensor | None = None):
+    """(out, count) of the elements of float32 x with x OP threshold, op in gt/ge/lt/le/eq/ne with IEEE semantics (NaN
+    is kept only by ne; the threshold is compared as float32). indices=True writes their int32 flat indices instead
+    of the values. No mask is materialised on the GPU. Does not synchronise."""
+    if op not in CMP_CODES:
+        raise ValueError(f"op must be one of {sorted(CMP_CODES)}, got {op!r}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x must be float32, got {x.dtype}")
+    _check_out(out, torch.int32 if indices else torch.float32, x.numel(), x)
+    if x.is_cuda:
+        return tuple(ops().select_if(x, CMP_CODES[op], float(threshold), bool(indices), out))
+    xf = x.reshape(-1)
+    keep = _CMP_TORCH[op](xf, torch.tensor(float(threshold), dtype=torch.float32))
+    kept = torch.nonzero(keep).reshape(-1).int() if indices else xf[keep]
+    return _host_result(kept, x.numel(), out)
