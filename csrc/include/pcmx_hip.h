@@ -104,6 +104,31 @@ int pcmx_select_index(const unsigned char* mask, int* out_idx, long long n, long
 int pcmx_select_if_f32(const float* x, int op, float threshold, void* out_or_idx, int want_index, long long n,
                        long long* count_dev, void* workspace, unsigned* err_flag, hipStream_t s);
 
+/* ---------------------------------------------------------------- radix sort (keys, pairs, argsort) */
+/* Stable LSD radix sort of n 32-bit keys, ascending (or descending != 0), by bits [begin_bit, end_bit) of the
+ * TRANSFORMED key; ceil((end_bit - begin_bit) / 8) one-sweep passes on the scan's look-back plus one histogram kernel
+ * (csrc/kernels/sort.hip). Bits outside the range are ignored; keys equal in the compared bits keep input order.
+ * Transformed key: U32 identity; I32 k ^ 0x80000000; F32 the order of torch.sort: ~b for a set sign bit, else
+ * b | 0x80000000, with -0.0 taking +0.0's key and every NaN (either sign, any payload) the key 0xffffffff, so NaNs
+ * sort last ascending, first descending, and signed zeros / NaNs tie. The transform is inverted on the last store:
+ * sorted F32 keys come out with +0.0 for both zeros and 0x7fffffff for every NaN (payloads are not preserved; gather
+ * with the indices to get the original bits). Values are 4 bytes moved as bits.
+ *   PCMX_SORT_KEYS   keys_out = sorted keys; vals_in / vals_out unused
+ *   PCMX_SORT_PAIRS  keys_out, vals_out = keys and their values
+ *   PCMX_SORT_INDEX  vals_out[j] = int32 input index of the j-th key (no iota array is read); keys_out may be NULL
+ *                    (the keys then ping-pong inside the workspace only)
+ * keys_in is never written and must not overlap an output; all pointers 16-B aligned; 0 < n < 2^30 (indices and the
+ * 30-bit granule counts; else PCMX_ERR_ARG); n <= 0 returns 0 and touches nothing. The workspace (16-B aligned,
+ * pcmx_sort_workspace_bytes) holds the flags, histograms and ping-pong buffers; one call in flight per workspace. Its
+ * header has the scan's layout: a look-back that gives up is reported as for pcmx_scan_f32 (pcmx_scan_check,
+ * *err_flag), and its result is invalid but every store stays inside the output buffers. */
+enum { PCMX_KEY_U32 = 0, PCMX_KEY_I32 = 1, PCMX_KEY_F32 = 2 };
+enum { PCMX_SORT_KEYS = 0, PCMX_SORT_PAIRS = 1, PCMX_SORT_INDEX = 2 };
+long long pcmx_sort_workspace_bytes(long long n, int mode);
+int pcmx_radix_sort(const void* keys_in, void* keys_out, const void* vals_in, void* vals_out, long long n,
+                    int key_type, int mode, int descending, int begin_bit, int end_bit,
+                    void* workspace, unsigned* err_flag, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

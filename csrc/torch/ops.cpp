@@ -325,6 +325,69 @@ std::tuple<at::Tensor, at::Tensor> select_if(const at::Tensor& x, int64_t op, do
     return select_finish(out, dest, count);
 }
 
+// ---------------------------------------------------------------- radix sort (keys, pairs, argsort)
+// Stable LSD radix sort of float32 / int32 keys by bits [begin_bit, end_bit) of the transformed key (pcmx_hip.h), sorted
+// as flattened 1-D; fresh 1-D outputs, the inputs are never written. Like the select ops: contiguous 16-B aligned inputs
+// (copied when they are not), workspace from the caching allocator, the per-(device, stream) sticky error word (so
+// scan_check() covers a sort whose look-back gave up), no host synchronisation.
+int sort_key_type(const at::Tensor& keys, const char* what) {
+    TORCH_CHECK(keys.is_cuda(), what, ": keys must be a GPU tensor");
+    TORCH_CHECK(keys.scalar_type() == at::kFloat || keys.scalar_type() == at::kInt, what, ": keys have dtype ",
+                keys.scalar_type(), ", expected float32 or int32");
+    return keys.scalar_type() == at::kFloat ? PCMX_KEY_F32 : PCMX_KEY_I32;
+}
+
+void sort_launch(const at::Tensor& keys, const at::Tensor* values, at::Tensor* keys_out, at::Tensor* vals_out, int mode,
+                 bool descending, int64_t begin_bit, int64_t end_bit, const char* what) {
+    const int key_type = sort_key_type(keys, what);
+    TORCH_CHECK(0 <= begin_bit && begin_bit < end_bit && end_bit <= 32, what, ": bit range [", begin_bit, ", ", end_bit, ")");
+    const int64_t n = keys.numel();
+    TORCH_CHECK(n < (1LL << 30), what, ": indices and granule counts are 30-bit, the keys must have fewer than 2^30 elements");
+    hipStream_t stream = cur_stream(keys);
+    unsigned* err_dev = scan_err_word(keys.device().index(), stream).dev;
+    raise_pending_scan_error(keys.device().index(), stream);
+    if (n == 0) return;
+    at::Tensor kc = aligned_contig(keys).view(-1), vc;
+    if (values) vc = aligned_contig(*values).view(-1);
+    auto ws = workspace(keys, pcmx_sort_workspace_bytes(n, mode));
+    check_rc(pcmx_radix_sort(kc.data_ptr(), keys_out ? keys_out->data_ptr() : nullptr, values ? vc.data_ptr() : nullptr,
+                             vals_out ? vals_out->data_ptr() : nullptr, n, key_type, mode, descending ? 1 : 0,
+                             (int)begin_bit, (int)end_bit, ws.data_ptr(), err_dev, stream),
+             what);
+}
+
+at::Tensor sort_keys(const at::Tensor& keys, bool descending, int64_t begin_bit, int64_t end_bit) {
+    sort_key_type(keys, "sort_keys");
+    const at::DeviceGuard g(keys.device());
+    at::Tensor out = at::empty({keys.numel()}, keys.options());
+    sort_launch(keys, nullptr, &out, nullptr, PCMX_SORT_KEYS, descending, begin_bit, end_bit, "sort_keys");
+    return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> sort_pairs(const at::Tensor& keys, const at::Tensor& values, bool descending,
+                                              int64_t begin_bit, int64_t end_bit) {
+    sort_key_type(keys, "sort_pairs");
+    TORCH_CHECK(values.device() == keys.device(), "sort_pairs: values must be on the keys' device");
+    TORCH_CHECK(values.scalar_type() == at::kFloat || values.scalar_type() == at::kInt, "sort_pairs: values have dtype ",
+                values.scalar_type(), ", expected float32 or int32");
+    TORCH_CHECK(values.numel() == keys.numel(), "sort_pairs: ", values.numel(), " values for ", keys.numel(), " keys");
+    const at::DeviceGuard g(keys.device());
+    at::Tensor ko = at::empty({keys.numel()}, keys.options()), vo = at::empty({keys.numel()}, values.options());
+    sort_launch(keys, &values, &ko, &vo, PCMX_SORT_PAIRS, descending, begin_bit, end_bit, "sort_pairs");
+    return {ko, vo};
+}
+
+// (sorted keys, int32 indices); with want_keys false the first tensor is empty and no sorted keys are written
+std::tuple<at::Tensor, at::Tensor> sort_index(const at::Tensor& keys, bool descending, int64_t begin_bit, int64_t end_bit,
+                                              bool want_keys) {
+    sort_key_type(keys, "sort_index");
+    const at::DeviceGuard g(keys.device());
+    at::Tensor ko = at::empty({want_keys ? keys.numel() : 0}, keys.options());
+    at::Tensor io = at::empty({keys.numel()}, keys.options().dtype(at::kInt));
+    sort_launch(keys, nullptr, want_keys ? &ko : nullptr, &io, PCMX_SORT_INDEX, descending, begin_bit, end_bit, "sort_index");
+    return {ko, io};
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -859,6 +922,9 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("select(Tensor x, Tensor mask, Tensor(a!)? out=None) -> (Tensor, Tensor)");
     m.def("select_index(Tensor mask, Tensor(a!)? out=None) -> (Tensor, Tensor)");
     m.def("select_if(Tensor x, int op, float threshold, bool indices=False, Tensor(a!)? out=None) -> (Tensor, Tensor)");
+    m.def("sort_keys(Tensor keys, bool descending=False, int begin_bit=0, int end_bit=32) -> Tensor");
+    m.def("sort_pairs(Tensor keys, Tensor values, bool descending=False, int begin_bit=0, int end_bit=32) -> (Tensor, Tensor)");
+    m.def("sort_index(Tensor keys, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor)");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -900,6 +966,9 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("select", select_b32);  // (::select is the POSIX call)
     m.impl("select_index", select_index);
     m.impl("select_if", select_if);
+    m.impl("sort_keys", sort_keys);
+    m.impl("sort_pairs", sort_pairs);
+    m.impl("sort_index", sort_index);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

@@ -639,8 +639,96 @@ class Select(Workload):
                 "lookback_ok": lookback_ok, "check_passed": ok and lookback_ok}
 
 
+class Sort(Workload):
+    """Stable radix sort of n keys per GPU (csrc/kernels/sort.hip): mode "keys" (sorted keys), "pairs" (keys with an
+    int32 payload) or "argsort" (int32 indices alone). dtype f32 (uniform in [-1, 1)) or i32 (uniform over the full range,
+    or over [0, 2^bits) with bits=B, which then runs ceil(B / 8) passes); dist "equal" makes every key the same (every
+    key in one digit bin: the worst case of the per-digit chain). No communication (weak scaling)."""
+
+    def __init__(self, ctx, n=1 << 28, mode="keys", dtype="f32", bits=None, descending=False, dist="uniform", **_):
+        if mode not in ("keys", "pairs", "argsort"):
+            raise ValueError(f"sort mode {mode!r}: keys, pairs or argsort")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"sort dtype {dtype!r}: f32 or i32")
+        if dist not in ("uniform", "equal"):
+            raise ValueError(f"sort dist {dist!r}: uniform or equal")
+        bits = None if bits is None else int(bits)
+        if bits is not None and dtype != "i32":
+            raise ValueError("sort bits is for i32 keys only")
+        super().__init__(ctx, {"n": int(n), "mode": mode, "dtype": dtype, "bits": bits, "descending": bool(descending),
+                               "dist": dist}, "sort", "GB/s")
+        n, dev = int(n), ctx.device
+        self.mode, self.bits, self.descending = mode, bits, bool(descending)
+        if dtype == "f32":
+            self.x = ops.rand_uniform_(torch.empty(n, device=dev), 9000 + ctx.rank, -1.0, 1.0)
+        else:
+            g = torch.Generator(device=dev).manual_seed(9000 + ctx.rank)
+            lo, hi = (0, 1 << bits) if bits is not None and bits < 32 else (-(1 << 31), 1 << 31)
+            self.x = torch.randint(lo, hi, (n,), device=dev, generator=g, dtype=torch.int64).to(torch.int32)
+        if dist == "equal":
+            self.x.fill_(0.5 if dtype == "f32" else 1)
+        self.payload = torch.arange(n, device=dev, dtype=torch.int32) if mode == "pairs" else None
+        self.out = None
+
+    def passes(self) -> int:
+        return (32 if self.bits is None else self.bits) + 7 >> 3
+
+    def step(self):
+        kw = {"descending": self.descending, "bits": self.bits}
+        if self.mode == "keys":
+            self.out = (ops.sort_keys(self.x, **kw),)
+        elif self.mode == "pairs":
+            self.out = ops.sort_by_key(self.x, self.payload, **kw)
+        else:
+            self.out = (ops.argsort(self.x, **kw),)
+
+    def torch_step(self):
+        """The torch call each mode replaces (the vendor bar)."""
+        if self.mode == "keys":
+            return torch.sort(self.x, descending=self.descending).values
+        r = torch.sort(self.x, stable=True, descending=self.descending)
+        return r.indices if self.mode == "argsort" else r
+
+    def work_per_step(self):
+        # bytes moved: the histogram reads the keys once; a pass reads and writes 4 bytes per key, and 4 more each way
+        # per value. An argsort's first pass reads no values (the index is computed), its last writes no keys.
+        n, p = self.x.numel(), self.passes()
+        per_pass = 8 if self.mode == "keys" else 16
+        skipped = 8 if self.mode == "argsort" else 0
+        return float(n * (4 + p * per_pass - skipped))
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gkeys_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        rep["passes"] = self.passes()
+        return rep
+
+    def check(self, reduce: bool = True):
+        """The outputs of the timed step against torch.sort(stable=True), exactly (indices and payload; keys bit for
+        bit: the generated keys hold no NaN and no -0.0), and the look-back error word of the stream. Local only."""
+        lookback_ok = True
+        if self.x.is_cuda:
+            try:
+                ops.scan_check(self.x.device)
+            except RuntimeError:
+                lookback_ok = False
+        ref = torch.sort(self.x, stable=True, descending=self.descending)
+        same = True
+        if self.mode != "argsort":
+            same = torch.equal(self.out[0].view(torch.int32), ref.values.view(torch.int32))
+        if self.mode != "keys":
+            same = same and self.out[-1].dtype == torch.int32 and torch.equal(self.out[-1], ref.indices.int())
+        ok = bool(same)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+            lookback_ok = self.ctx.max_over_ranks(0.0 if lookback_ok else 1.0) == 0.0
+        return {"elements_checked": self.x.numel(), "exact_vs_torch": ok, "lookback_ok": lookback_ok,
+                "check_passed": ok and lookback_ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
-             "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select}
+             "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
+             "sort": Sort}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:
