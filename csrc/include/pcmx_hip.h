@@ -129,6 +129,30 @@ int pcmx_radix_sort(const void* keys_in, void* keys_out, const void* vals_in, vo
                     int key_type, int mode, int descending, int begin_bit, int end_bit,
                     void* workspace, unsigned* err_flag, hipStream_t s);
 
+/* ---------------------------------------------------------------- run-length encode / reduce by key */
+/* Collapses runs of equal neighbouring 32-bit keys of a length-n stream and reduces a value stream per run, in one pass
+ * on the scan's decoupled look-back plus a small kernel that joins the runs crossing tile borders
+ * (csrc/kernels/segreduce.hip). Keys are compared as BIT PATTERNS: -0.0 and +0.0 are different keys, two NaNs with
+ * the same bits are the same key (torch.unique_consecutive on the int32 view, not on the float view; the sorted float
+ * keys of pcmx_radix_sort are canonical, so they collapse as values). A run is a maximal block of equal neighbours;
+ * element 0 starts one. The number of runs goes to *num_runs_dev (int64, device memory) without a host sync; every
+ * per-run array needs room for n entries and only [0, num_runs) is written. Run keys keep their exact bits; counts
+ * and start offsets are int32. op is PCMX_OP_SUM / MIN / MAX: int32 sums wrap mod 2^32 and int32 results are exact;
+ * float32 results depend only on the input, never on timing (fixed association order, no float atomics); float
+ * min / max hand on a NaN value (which NaN's payload is unspecified). keys, vals and every output 16-B aligned,
+ * 0 < n < 2^31 and a valid op (else PCMX_ERR_ARG, nothing launched); n <= 0 stores 0 runs and launches nothing else.
+ * No output may overlap an input. The workspace header has the scan's layout: a look-back that gives up is reported
+ * as for pcmx_scan_f32 (pcmx_scan_check, *err_flag); its result is invalid but every store stays inside the outputs. */
+long long pcmx_segreduce_workspace_bytes(long long n);
+/* run_keys[j], counts[j] (and starts[j], the offset of the run's first element, when starts != NULL) of the j-th run */
+int pcmx_run_length_encode_b32(const void* keys, long long n, void* run_keys, int* counts, int* starts,
+                               long long* num_runs_dev, void* workspace, unsigned* err_flag, hipStream_t s);
+/* agg[j] = op over the values of the j-th run; run_keys may be NULL (the keys of the runs are then not written) */
+int pcmx_reduce_by_key_f32(const void* keys, const float* vals, long long n, int op, void* run_keys, float* agg,
+                           long long* num_runs_dev, void* workspace, unsigned* err_flag, hipStream_t s);
+int pcmx_reduce_by_key_i32(const void* keys, const int32_t* vals, long long n, int op, void* run_keys, int32_t* agg,
+                           long long* num_runs_dev, void* workspace, unsigned* err_flag, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

@@ -388,6 +388,86 @@ std::tuple<at::Tensor, at::Tensor> sort_index(const at::Tensor& keys, bool desce
     return {ko, io};
 }
 
+// ---------------------------------------------------------------- run-length encode / reduce by key
+// Runs of equal neighbouring keys (compared as bit patterns) of the flattened input, one pass on the scan's look-back
+// (csrc/kernels/segreduce.hip). Like the select ops: per-run outputs have room for keys.numel() entries, the run count
+// is a 0-d int64 tensor on the device, nothing synchronises, optional caller outputs are left untouched past the
+// count, and the per-(device, stream) sticky error word is shared, so scan_check() covers these ops too.
+struct SegPrep {
+    at::Tensor keys;
+    hipStream_t stream;
+    unsigned* err_dev;
+    int64_t n;
+};
+
+SegPrep seg_prepare(const at::Tensor& keys, const char* what) {
+    sort_key_type(keys, what);
+    TORCH_CHECK(keys.numel() < (1LL << 31), what, ": offsets are int32, the keys must have fewer than 2^31 elements");
+    SegPrep p;
+    p.stream = cur_stream(keys);
+    p.err_dev = scan_err_word(keys.device().index(), p.stream).dev;
+    raise_pending_scan_error(keys.device().index(), p.stream);
+    p.n = keys.numel();
+    p.keys = aligned_contig(keys).view(-1);
+    return p;
+}
+
+// (run_keys, counts, starts, num_runs); starts is an empty tensor unless want_starts
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> run_length_encode(
+    const at::Tensor& keys, bool want_starts, const c10::optional<at::Tensor>& out_keys,
+    const c10::optional<at::Tensor>& out_counts, const c10::optional<at::Tensor>& out_starts) {
+    const at::DeviceGuard g(keys.device());
+    SegPrep p = seg_prepare(keys, "run_length_encode");
+    at::Tensor dk = select_dest(out_keys, keys, keys.scalar_type(), p.n, "run_length_encode");
+    at::Tensor dc = select_dest(out_counts, keys, at::kInt, p.n, "run_length_encode");
+    at::Tensor ds = want_starts ? select_dest(out_starts, keys, at::kInt, p.n, "run_length_encode")
+                                : at::empty({0}, keys.options().dtype(at::kInt));
+    if (overlaps(p.keys, dk) || overlaps(p.keys, dc) || (want_starts && overlaps(p.keys, ds))) p.keys = p.keys.clone();
+    at::Tensor count = at::empty({}, keys.options().dtype(at::kLong));
+    auto ws = workspace(keys, pcmx_segreduce_workspace_bytes(p.n));
+    check_rc(pcmx_run_length_encode_b32(p.keys.data_ptr(), p.n, dk.data_ptr(), dc.data_ptr<int>(),
+                                        want_starts ? ds.data_ptr<int>() : nullptr, (long long*)count.data_ptr<int64_t>(),
+                                        ws.data_ptr(), p.err_dev, p.stream),
+             "run_length_encode");
+    at::Tensor rk = std::get<0>(select_finish(out_keys, dk, count));
+    at::Tensor rc = std::get<0>(select_finish(out_counts, dc, count));
+    at::Tensor rs = want_starts ? std::get<0>(select_finish(out_starts, ds, count)) : ds;
+    return {rk, rc, rs, count};
+}
+
+// (run_keys, aggregates, num_runs)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> reduce_by_key(const at::Tensor& keys, const at::Tensor& values, int64_t op,
+                                                             const c10::optional<at::Tensor>& out_keys,
+                                                             const c10::optional<at::Tensor>& out) {
+    const at::DeviceGuard g(keys.device());
+    SegPrep p = seg_prepare(keys, "reduce_by_key");
+    TORCH_CHECK(op >= PCMX_OP_SUM && op <= PCMX_OP_MAX, "reduce_by_key: op code ", op);
+    TORCH_CHECK(values.device() == keys.device(), "reduce_by_key: values must be on the keys' device");
+    TORCH_CHECK(values.scalar_type() == at::kFloat || values.scalar_type() == at::kInt, "reduce_by_key: values have dtype ",
+                values.scalar_type(), ", expected float32 or int32");
+    TORCH_CHECK(values.numel() == p.n, "reduce_by_key: ", values.numel(), " values for ", p.n, " keys");
+    at::Tensor vc = aligned_contig(values).view(-1);
+    at::Tensor dk = select_dest(out_keys, keys, keys.scalar_type(), p.n, "reduce_by_key");
+    at::Tensor da = select_dest(out, values, values.scalar_type(), p.n, "reduce_by_key");
+    if (overlaps(p.keys, dk) || overlaps(p.keys, da)) p.keys = p.keys.clone();
+    if (overlaps(vc, dk) || overlaps(vc, da)) vc = vc.clone();
+    at::Tensor count = at::empty({}, keys.options().dtype(at::kLong));
+    auto ws = workspace(keys, pcmx_segreduce_workspace_bytes(p.n));
+    if (values.scalar_type() == at::kFloat)
+        check_rc(pcmx_reduce_by_key_f32(p.keys.data_ptr(), vc.data_ptr<float>(), p.n, (int)op, dk.data_ptr(),
+                                        da.data_ptr<float>(), (long long*)count.data_ptr<int64_t>(), ws.data_ptr(),
+                                        p.err_dev, p.stream),
+                 "reduce_by_key");
+    else
+        check_rc(pcmx_reduce_by_key_i32(p.keys.data_ptr(), vc.data_ptr<int32_t>(), p.n, (int)op, dk.data_ptr(),
+                                        da.data_ptr<int32_t>(), (long long*)count.data_ptr<int64_t>(), ws.data_ptr(),
+                                        p.err_dev, p.stream),
+                 "reduce_by_key");
+    at::Tensor rk = std::get<0>(select_finish(out_keys, dk, count));
+    at::Tensor ra = std::get<0>(select_finish(out, da, count));
+    return {rk, ra, count};
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -925,6 +1005,8 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("sort_keys(Tensor keys, bool descending=False, int begin_bit=0, int end_bit=32) -> Tensor");
     m.def("sort_pairs(Tensor keys, Tensor values, bool descending=False, int begin_bit=0, int end_bit=32) -> (Tensor, Tensor)");
     m.def("sort_index(Tensor keys, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor)");
+    m.def("run_length_encode(Tensor keys, bool starts=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_counts=None, Tensor(c!)? out_starts=None) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("reduce_by_key(Tensor keys, Tensor values, int op, Tensor(a!)? out_keys=None, Tensor(b!)? out=None) -> (Tensor, Tensor, Tensor)");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -969,6 +1051,8 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("sort_keys", sort_keys);
     m.impl("sort_pairs", sort_pairs);
     m.impl("sort_index", sort_index);
+    m.impl("run_length_encode", run_length_encode);
+    m.impl("reduce_by_key", reduce_by_key);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

@@ -726,9 +726,131 @@ class Sort(Workload):
                 "check_passed": ok and lookback_ok}
 
 
+class SegReduce(Workload):
+    """Runs of equal neighbouring keys of n elements per GPU (csrc/kernels/segreduce.hip): mode "rle" (run keys and
+    lengths of keys of dtype f32 / i32), "sum" (int32 keys, the values of dtype f32 / i32 summed per run) or "unique"
+    (sorted distinct values and counts of an unsorted input: sort, then collapse). Element i starts a run when a seeded
+    counter falls below 1 / mean_run, so run lengths are geometric with mean mean_run; mean_run=0 makes every key
+    equal (one run across every tile). In "unique" the input is n draws from about n / mean_run values. No
+    communication (weak scaling)."""
+
+    def __init__(self, ctx, n=1 << 28, mean_run=4.0, mode="rle", dtype="f32", **_):
+        if mode not in ("rle", "sum", "unique"):
+            raise ValueError(f"segreduce mode {mode!r}: rle, sum or unique")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"segreduce dtype {dtype!r}: f32 or i32")
+        if float(mean_run) < 0 or 0 < float(mean_run) < 1:
+            raise ValueError(f"segreduce mean_run {mean_run!r}: 0 (all keys equal) or >= 1")
+        super().__init__(ctx, {"n": int(n), "mean_run": float(mean_run), "mode": mode, "dtype": dtype}, "segreduce", "GB/s")
+        n, dev, mean_run = int(n), ctx.device, float(mean_run)
+        self.mode = mode
+        tdt = torch.float32 if dtype == "f32" else torch.int32
+        u = ops.rand_uniform_(torch.empty(n, device=dev), 10000 + ctx.rank, 0.0, 1.0)  # the seeded counter
+        if mode == "unique":
+            groups = max(1, int(n / mean_run)) if mean_run else 1
+            ids = (u.double() * groups).long().clamp_(max=groups - 1)
+        else:
+            ids = torch.cumsum(u < (1.0 / mean_run if mean_run else 0.0), 0)  # neighbouring runs get different ids
+        del u
+        ids = (ids % (1 << 24)).int()  # exact as float32 too (consecutive ids stay different)
+        self.keys = ids.to(tdt) if mode != "sum" else ids
+        del ids
+        self.values = None
+        if mode == "sum":
+            v = ops.rand_uniform_(torch.empty(n, device=dev), 11000 + ctx.rank, 0.0, 1.0)
+            self.values = v if dtype == "f32" else (v * 1000.0).int()
+        self.out = None
+
+    def step(self):
+        if self.mode == "rle":
+            self.out = ops.run_length_encode(self.keys)
+        elif self.mode == "sum":
+            self.out = ops.reduce_by_key(self.keys, self.values, "sum")
+        else:
+            rk, rc, num = ops.run_length_encode(ops.sort_keys(self.keys))
+            self.out = (rk, rc, num)
+
+    def torch_step(self):
+        """The torch calls each mode replaces (the vendor bar; they synchronise for the size of their result)."""
+        if self.mode == "rle":
+            return torch.unique_consecutive(self.keys, return_counts=True)
+        if self.mode == "sum":
+            rk, inv = torch.unique_consecutive(self.keys, return_inverse=True)
+            return rk, torch.zeros(rk.numel(), dtype=self.values.dtype, device=rk.device).index_add_(0, inv, self.values)
+        return torch.unique(self.keys, return_counts=True)
+
+    def runs(self) -> int:
+        return int(self.out[-1].item()) if self.out is not None else 0
+
+    def work_per_step(self):
+        # bytes moved: the keys (and values) once, 8 bytes out per run; unique adds the sort's histogram read and four
+        # read + write passes over the keys
+        n, k = self.keys.numel(), self.runs()
+        return float({"rle": 4 * n, "sum": 8 * n, "unique": (4 + 4 * 8 + 4) * n}[self.mode] + 8 * k)
+
+    def _ref_chunks(self, chunk: int):
+        """(key bits, per-run reference, chunk continues the previous run) of torch on each input chunk. The per-run
+        reference is the int64 run length (rle) or the int64 / float64 sum (sum)."""
+        n = self.keys.numel()
+        kb = self.keys.view(torch.int32)
+        for s in range(0, n, chunk):
+            e = min(n, s + chunk)
+            rk, inv, cnt = torch.unique_consecutive(kb[s:e], return_inverse=True, return_counts=True)
+            if self.mode == "sum":
+                acc = torch.float64 if self.values.dtype == torch.float32 else torch.int64
+                cnt = torch.zeros(rk.numel(), dtype=acc, device=rk.device).index_add_(0, inv, self.values[s:e].to(acc))
+            yield rk, cnt, bool(s > 0 and (kb[s] == kb[s - 1]).item())
+
+    def _same(self, got: torch.Tensor, ref: torch.Tensor) -> bool:
+        if ref.dtype == torch.float64:  # float32 sums: the fp64 sum of the same values, to REL_ERR_LIMIT
+            return bool(((got.double() - ref).abs() <= REL_ERR_LIMIT * ref.abs().clamp_min(1.0)).all())
+        return torch.equal(got.long(), ((ref + (1 << 31)) % (1 << 32)) - (1 << 31))  # int32 sums wrap
+
+    def check(self, reduce: bool = True, chunk: int = 1 << 26):
+        """Every output of the timed step against torch, chunk by chunk: run keys bit for bit and run lengths / int32
+        sums exactly (runs that cross a chunk border are joined), float32 sums against the fp64 sums to REL_ERR_LIMIT,
+        unique against torch.unique(return_counts=True); and the look-back error word of the stream. Local only."""
+        lookback_ok = True
+        if self.keys.is_cuda:
+            try:
+                ops.scan_check(self.keys.device)
+            except RuntimeError:
+                lookback_ok = False
+        k, pos, same = self.runs(), 0, True
+        okeys, oagg = self.out[0].view(torch.int32), self.out[1]
+        if self.mode == "unique":
+            rv, rc = torch.unique(self.keys, return_counts=True)
+            pos = rv.numel()
+            for s in range(0, pos if pos == k else 0, chunk):
+                e = min(pos, s + chunk)
+                same = same and torch.equal(okeys[s:e], rv.view(torch.int32)[s:e]) and torch.equal(oagg[s:e].long(), rc[s:e])
+        else:
+            pend_k = pend_v = None  # the last run of the chunks so far: it may go on in the next chunk
+            for rk, rv, joins in self._ref_chunks(chunk):
+                if pend_k is not None:
+                    if joins:
+                        rv[0] += pend_v[0]
+                    else:
+                        rk, rv = torch.cat([pend_k, rk]), torch.cat([pend_v, rv])
+                m = rk.numel() - 1
+                same = same and pos + m < k and torch.equal(okeys[pos:pos + m], rk[:m]) \
+                    and self._same(oagg[pos:pos + m], rv[:m])
+                pos += m
+                pend_k, pend_v = rk[m:], rv[m:]
+            if pend_k is not None:
+                same = same and pos < k and torch.equal(okeys[pos:pos + 1], pend_k) and self._same(oagg[pos:pos + 1], pend_v)
+                pos += 1
+        ok = bool(same and pos == k)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+            lookback_ok = self.ctx.max_over_ranks(0.0 if lookback_ok else 1.0) == 0.0
+        return {"runs": k, "runs_torch": pos, "elements_checked": self.keys.numel(), "matches_torch": ok,
+                "lookback_ok": lookback_ok, "check_passed": ok and lookback_ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
-             "sort": Sort}
+             "sort": Sort, "segreduce": SegReduce}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

@@ -318,3 +318,134 @@ def sort_by_key(keys: torch.Tensor, values: torch.Tensor, descending: bool = Fal
     # (indexing an int32 view: a float gather would be free to quieten a signalling NaN payload)
     vbits = values.reshape(-1).view(torch.int32)[order]
     return _canonical_f32(kf[order]), vbits.view(values.dtype)
+
+
+# ---------------------------------------------------------------- run-length encode / reduce by key / unique
+# Collapse runs of equal neighbouring keys of the flattened input and reduce a value stream per run. On the GPU one
+# pass on the scan's decoupled look-back carrying the exact integer count of run heads, a segmented reduction inside
+# each 32768-key tile, and a small second kernel that joins the runs crossing tile borders in a fixed order
+# (csrc/kernels/segreduce.hip); no counterpart in the reference programs. The by-key members of the scan / select /
+# sort family: unique and sum_by_key are "sort, then collapse".
+#  * KEY RULE: keys (float32 or int32) are compared as 32-bit PATTERNS. -0.0 and +0.0 are different keys; two NaNs with
+#    the same bits are the same key, NaNs with different payloads are different keys. This is torch.unique_consecutive
+#    on the int32 view, not on the float view. sort_keys output is canonical (one zero, one NaN), so sorted float keys
+#    collapse as values.
+#  * A run is a maximal block of equal neighbours; element 0 starts one; an empty input has 0 runs.
+#  * run_length_encode / reduce_by_key follow compact's (out, count) contract: per-run outputs have room for every
+#    element, only [:num_runs] is written, num_runs is a 0-d int64 tensor on the input's device, nothing synchronises;
+#    a look-back that gave up is reported by scan_check(). Run keys keep their exact bits; counts and starts are int32.
+#  * int32 sums wrap mod 2^32 and int32 results are exact. A float32 result depends only on the input, never on
+#    timing: the same call gives the same bits (fixed association order, no float atomics).
+#  * Measured against torch on one MI355X at 2^28 int32 keys, mean run length 1 to 10^5 and all equal
+#    (profiles/r9_segreduce/README.md): run_length_encode 1.01-1.33x faster than torch.unique_consecutive with counts,
+#    reduce_by_key sums 3.4x-108x faster than unique_consecutive + index_add_. unique(return_counts=True) is SLOWER
+#    than torch.unique: 6.22-7.39 ms against 6.15-6.21 ms (0.83-0.99x), level only when all keys are equal.
+def _check_seg_keys(keys: torch.Tensor, name: str = "keys") -> None:
+    if keys.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name} must be float32 or int32, got {keys.dtype}")
+    if keys.numel() >= 1 << 31:
+        raise ValueError(f"{name} has {keys.numel()} elements; run offsets are int32 (fewer than 2^31)")
+
+
+def _host_runs(keys: torch.Tensor):
+    """(run key bits, int64 run index of every element, int64 run lengths) of flat keys compared as bit patterns."""
+    bits = keys.reshape(-1).contiguous().view(torch.int32)
+    return torch.unique_consecutive(bits, return_inverse=True, return_counts=True)
+
+
+def run_length_encode(keys: torch.Tensor, starts: bool = False, out_keys: torch.Tensor | None = None,
+                      out_counts: torch.Tensor | None = None, out_starts: torch.Tensor | None = None):
+    """(run_keys, counts, num_runs), or (run_keys, counts, starts, num_runs) with starts=True: the key, the int32
+    length and the int32 offset of the first element of every run of equal neighbouring keys of keys.flatten(). Keys
+    (float32 or int32) are compared as bit patterns: -0.0 != +0.0, NaNs are equal only with equal bits. num_runs is a
+    0-d int64 tensor on the keys' device; the per-run tensors (or the optional caller tensors out_*, 1-D with room for
+    keys.numel() entries) are written only in [:num_runs]. Does not synchronise."""
+    _check_seg_keys(keys)
+    n = keys.numel()
+    _check_out(out_keys, keys.dtype, n, keys)
+    _check_out(out_counts, torch.int32, n, keys)
+    if starts:
+        _check_out(out_starts, torch.int32, n, keys)
+    if keys.is_cuda:
+        rk, rc, rs, num = ops().run_length_encode(keys, bool(starts), out_keys, out_counts, out_starts if starts else None)
+        return (rk, rc, rs, num) if starts else (rk, rc, num)
+    kbits, _, counts = _host_runs(keys)
+    rk, num = _host_result(kbits.view(keys.dtype), n, out_keys)
+    rc, _ = _host_result(counts.int(), n, out_counts)
+    if not starts:
+        return rk, rc, num
+    rs, _ = _host_result((torch.cumsum(counts, 0) - counts).int(), n, out_starts)
+    return rk, rc, rs, num
+
+
+def _check_seg_values(keys: torch.Tensor, values: torch.Tensor) -> None:
+    if values.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"values must be float32 or int32, got {values.dtype}")
+    if values.numel() != keys.numel():
+        raise ValueError(f"{values.numel()} values for {keys.numel()} keys")
+    if values.device != keys.device:
+        raise ValueError(f"values are on {values.device}, the keys on {keys.device}")
+
+
+def reduce_by_key(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", out_keys: torch.Tensor | None = None,
+                  out: torch.Tensor | None = None):
+    """(run_keys, aggregates, num_runs): values (float32 or int32, same numel) reduced with op (sum, min, max) over
+    every run of equal neighbouring keys of keys.flatten(); keys compared as bit patterns (-0.0 != +0.0, NaNs equal only
+    with equal bits). int32 sums wrap mod 2^32; int32 results are exact. A float32 sum uses a fixed association order
+    (not input order): the same input gives the same bits on every call, whatever the timing. float32 min / max
+    propagate a NaN value (like torch's amin / amax; which NaN's payload comes out is unspecified). Outputs follow
+    run_length_encode's contract; does not synchronise."""
+    _check_seg_keys(keys)
+    if op not in OP_CODES:
+        raise ValueError(f"op must be one of {sorted(OP_CODES)}, got {op!r}")
+    _check_seg_values(keys, values)
+    n = keys.numel()
+    _check_out(out_keys, keys.dtype, n, keys)
+    _check_out(out, values.dtype, n, keys)
+    if keys.is_cuda:
+        return tuple(ops().reduce_by_key(keys, values, OP_CODES[op], out_keys, out))
+    kbits, inv, _ = _host_runs(keys)
+    k, vf = kbits.numel(), values.reshape(-1)
+    if op == "sum" and values.dtype == torch.int32:
+        s = torch.zeros(k, dtype=torch.int64).index_add_(0, inv, vf.long())
+        agg = (((s + (1 << 31)) % (1 << 32)) - (1 << 31)).int()
+    elif op == "sum":
+        agg = torch.zeros(k, dtype=torch.float32).index_add_(0, inv, vf)
+    else:
+        agg = torch.zeros(k, dtype=values.dtype).scatter_reduce_(0, inv, vf, "amin" if op == "min" else "amax",
+                                                                 include_self=False)
+    rk, num = _host_result(kbits.view(keys.dtype), n, out_keys)
+    ra, _ = _host_result(agg, n, out)
+    return rk, ra, num
+
+
+def unique_consecutive(keys: torch.Tensor, return_counts: bool = False):
+    """The key of every run of equal neighbouring keys of keys.flatten() at exact size (one host sync for the count),
+    with the int32 run lengths when return_counts. Keys are compared as bit patterns: torch.unique_consecutive on the
+    int32 view (-0.0 and +0.0 stay apart, NaNs collapse only with equal bits)."""
+    rk, rc, num = run_length_encode(keys)
+    k = int(num.item())
+    return (rk[:k], rc[:k]) if return_counts else rk[:k]
+
+
+def unique(x: torch.Tensor, return_counts: bool = False):
+    """The sorted distinct values of x.flatten() (float32 or int32, at most SORT_MAX_N elements) at exact size, with
+    their int32 counts when return_counts: sort_keys, then run_length_encode (one host sync). For float32 the two
+    zeros are ONE value (+0.0) and all NaNs are ONE value (bits 0x7fffffff, last), because sort_keys output is
+    canonical; torch.unique keeps every NaN as a value of its own. On an MI355X this is slower than torch.unique
+    (2^28 int32 keys: 6.22-7.39 ms against 6.15-6.21 ms; the sort dominates)."""
+    rk, rc, num = run_length_encode(sort_keys(x))
+    k = int(num.item())
+    return (rk[:k], rc[:k]) if return_counts else rk[:k]
+
+
+def sum_by_key(keys: torch.Tensor, values: torch.Tensor):
+    """(unique_keys, sums) at exact size: the unsorted group-by sum, sort_by_key followed by reduce_by_key (one host
+    sync). Keys as in unique (float32 zeros and NaNs are one group each). The sort is stable, so the values of equal
+    keys meet the reduction in input order; a float32 sum is then reduce_by_key's fixed association over that
+    sequence (deterministic, not a left-to-right sum). int32 sums wrap."""
+    _check_seg_values(keys, values)
+    ks, vs = sort_by_key(keys, values)
+    rk, ra, num = reduce_by_key(ks, vs, "sum")
+    k = int(num.item())
+    return rk[:k], ra[:k]
