@@ -129,6 +129,27 @@ int pcmx_radix_sort(const void* keys_in, void* keys_out, const void* vals_in, vo
                     int key_type, int mode, int descending, int begin_bit, int end_bit,
                     void* workspace, unsigned* err_flag, hipStream_t s);
 
+/* ---------------------------------------------------------------- top-k / k-th value (radix select) */
+/* The k best of n 32-bit keys, largest != 0: the largest, else the smallest, in the order of pcmx_radix_sort's
+ * transformed keys (F32: -0.0 == +0.0, every NaN one key above +inf). The result is DEFINED as the first k entries of
+ * the stable PCMX_SORT_INDEX sort with descending = largest: among keys that tie with the k-th key the lowest indices
+ * are taken, ties come out in ascending index order, F32 values come out canonical (+0.0, NaN bits 0x7fffffff).
+ * out_vals[j] / out_idx[j] (int32 flat index), j < k. sorted == 0: the same k elements in ascending index order (no
+ * survivor sort runs). The keys are never written and must not overlap an output. Four histogram passes find the k-th
+ * key (most significant digit first, the digit chosen on the device; no inter-block waiting), one pass on the scan's
+ * look-back gathers the k survivors in index order, pcmx_radix_sort orders them (csrc/kernels/topk.hip). No host sync.
+ * keys, outputs and workspace 16-B aligned, 0 < n < 2^30, 0 <= k <= n, a valid key type (else PCMX_ERR_ARG, nothing
+ * launched); n == 0 or k == 0 returns 0 without a launch. The workspace header has the scan's layout: a look-back that
+ * gives up is reported as for pcmx_scan_f32 (pcmx_scan_check, *err_flag); its result is invalid but every store stays
+ * inside the k-element outputs. One call in flight per workspace. */
+long long pcmx_topk_workspace_bytes(long long n, long long k, int sorted);
+int pcmx_topk_b32(const void* keys, long long n, long long k, int key_type, int largest, int sorted, void* out_vals,
+                  void* out_idx, void* workspace, unsigned* err_flag, hipStream_t s);
+/* out_dev[0] = the k-th key (1 <= k <= n, 1-based; the k-th largest when largest != 0), canonical as above: the
+ * histogram passes alone. Workspace: pcmx_topk_workspace_bytes(n, k, 0). err_flag is unused (no look-back runs). */
+int pcmx_kth_key_b32(const void* keys, long long n, long long k, int key_type, int largest, void* out_dev,
+                     void* workspace, unsigned* err_flag, hipStream_t s);
+
 /* ---------------------------------------------------------------- run-length encode / reduce by key */
 /* Collapses runs of equal neighbouring 32-bit keys of a length-n stream and reduces a value stream per run, in one pass
  * on the scan's decoupled look-back plus a small kernel that joins the runs crossing tile borders

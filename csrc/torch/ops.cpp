@@ -388,6 +388,48 @@ std::tuple<at::Tensor, at::Tensor> sort_index(const at::Tensor& keys, bool desce
     return {ko, io};
 }
 
+// ---------------------------------------------------------------- top-k / k-th value (radix select)
+// The first k entries of the stable sort of the flattened keys (descending = largest) without sorting them: four
+// histogram passes find the k-th key, one look-back pass gathers the k survivors, a pair sort orders them
+// (csrc/kernels/topk.hip). Like sort_launch: contiguous 16-B aligned input (copied when it is not), workspace from the
+// caching allocator, the per-(device, stream) sticky error word, no host synchronisation.
+std::tuple<at::Tensor, at::Tensor> topk(const at::Tensor& x, int64_t k, bool largest, bool sorted) {
+    const int key_type = sort_key_type(x, "topk");
+    const int64_t n = x.numel();
+    TORCH_CHECK(n < (1LL << 30), "topk: the keys must have fewer than 2^30 elements");
+    TORCH_CHECK(0 <= k && k <= n, "topk: k = ", k, " for ", n, " elements");
+    const at::DeviceGuard g(x.device());
+    hipStream_t stream = cur_stream(x);
+    unsigned* err_dev = scan_err_word(x.device().index(), stream).dev;
+    raise_pending_scan_error(x.device().index(), stream);
+    at::Tensor vals = at::empty({k}, x.options()), idx = at::empty({k}, x.options().dtype(at::kInt));
+    if (k == 0) return {vals, idx};
+    at::Tensor xc = aligned_contig(x).view(-1);
+    auto ws = workspace(x, pcmx_topk_workspace_bytes(n, k, sorted ? 1 : 0));
+    check_rc(pcmx_topk_b32(xc.data_ptr(), n, k, key_type, largest ? 1 : 0, sorted ? 1 : 0, vals.data_ptr(), idx.data_ptr(),
+                           ws.data_ptr(), err_dev, stream),
+             "topk");
+    return {vals, idx};
+}
+
+// the k-th key (1-based) as a 0-d tensor: the histogram passes alone
+at::Tensor kth_value(const at::Tensor& x, int64_t k, bool largest) {
+    const int key_type = sort_key_type(x, "kth_value");
+    const int64_t n = x.numel();
+    TORCH_CHECK(n < (1LL << 30), "kth_value: the keys must have fewer than 2^30 elements");
+    TORCH_CHECK(1 <= k && k <= n, "kth_value: k = ", k, " for ", n, " elements");
+    const at::DeviceGuard g(x.device());
+    hipStream_t stream = cur_stream(x);
+    unsigned* err_dev = scan_err_word(x.device().index(), stream).dev;
+    raise_pending_scan_error(x.device().index(), stream);
+    at::Tensor out = at::empty({}, x.options());
+    at::Tensor xc = aligned_contig(x).view(-1);
+    auto ws = workspace(x, pcmx_topk_workspace_bytes(n, k, 0));
+    check_rc(pcmx_kth_key_b32(xc.data_ptr(), n, k, key_type, largest ? 1 : 0, out.data_ptr(), ws.data_ptr(), err_dev, stream),
+             "kth_value");
+    return out;
+}
+
 // ---------------------------------------------------------------- run-length encode / reduce by key
 // Runs of equal neighbouring keys (compared as bit patterns) of the flattened input, one pass on the scan's look-back
 // (csrc/kernels/segreduce.hip). Like the select ops: per-run outputs have room for keys.numel() entries, the run count
@@ -1005,6 +1047,8 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("sort_keys(Tensor keys, bool descending=False, int begin_bit=0, int end_bit=32) -> Tensor");
     m.def("sort_pairs(Tensor keys, Tensor values, bool descending=False, int begin_bit=0, int end_bit=32) -> (Tensor, Tensor)");
     m.def("sort_index(Tensor keys, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor)");
+    m.def("topk(Tensor x, int k, bool largest=True, bool sorted=True) -> (Tensor, Tensor)");
+    m.def("kth_value(Tensor x, int k, bool largest=False) -> Tensor");
     m.def("run_length_encode(Tensor keys, bool starts=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_counts=None, Tensor(c!)? out_starts=None) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("reduce_by_key(Tensor keys, Tensor values, int op, Tensor(a!)? out_keys=None, Tensor(b!)? out=None) -> (Tensor, Tensor, Tensor)");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
@@ -1051,6 +1095,8 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("sort_keys", sort_keys);
     m.impl("sort_pairs", sort_pairs);
     m.impl("sort_index", sort_index);
+    m.impl("topk", topk);
+    m.impl("kth_value", kth_value);
     m.impl("run_length_encode", run_length_encode);
     m.impl("reduce_by_key", reduce_by_key);
     m.impl("sgemm", sgemm);

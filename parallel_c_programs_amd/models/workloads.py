@@ -848,9 +848,83 @@ class SegReduce(Workload):
                 "lookback_ok": lookback_ok, "check_passed": ok and lookback_ok}
 
 
+class TopK(Workload):
+    """The k best of n keys per GPU and their indices (csrc/kernels/topk.hip): dtype f32 (uniform in [-1, 1)) or i32
+    (uniform over the full range); dist "equal" makes every key the same (every key ties with the k-th: the gather
+    takes the first k indices), "sorted" sorts the keys ascending (the best are the last, or with largest=False the
+    first, tiles). method is ops.topk's (None, "select", "sort"). No communication (weak scaling)."""
+
+    def __init__(self, ctx, n=1 << 28, k=1024, dtype="f32", largest=True, sorted=True, dist="uniform", method=None,
+                 **_):
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"topk dtype {dtype!r}: f32 or i32")
+        if dist not in ("uniform", "equal", "sorted"):
+            raise ValueError(f"topk dist {dist!r}: uniform, equal or sorted")
+        n, k, dev = int(n), int(k), ctx.device
+        if not 0 <= k <= n:
+            raise ValueError(f"topk k {k}: 0..{n}")
+        super().__init__(ctx, {"n": n, "k": k, "dtype": dtype, "largest": bool(largest), "sorted": bool(sorted),
+                               "dist": dist, "method": method}, "topk", "GB/s")
+        self.k, self.largest, self.sorted, self.method = k, bool(largest), bool(sorted), method
+        if dtype == "f32":
+            self.x = ops.rand_uniform_(torch.empty(n, device=dev), 12000 + ctx.rank, -1.0, 1.0)
+        else:
+            g = torch.Generator(device=dev).manual_seed(12000 + ctx.rank)
+            self.x = torch.randint(-(1 << 31), 1 << 31, (n,), device=dev, generator=g, dtype=torch.int64).to(torch.int32)
+        if dist == "equal":
+            self.x.fill_(0.5 if dtype == "f32" else 1)
+        elif dist == "sorted":
+            self.x = torch.sort(self.x).values
+        self.out = None
+
+    def step(self):
+        self.out = ops.topk(self.x, self.k, self.largest, self.sorted, method=self.method)
+
+    def torch_step(self):
+        """The torch call this replaces (the vendor bar; its choice among ties is unspecified)."""
+        return torch.topk(self.x, self.k, largest=self.largest, sorted=self.sorted)
+
+    def work_per_step(self):
+        # bytes the select route really reads and writes: four histogram passes and the gather read the keys once each;
+        # the gather writes 8 bytes per survivor; the survivor sort reads them once for its histogram and reads and
+        # writes them in each of its four passes
+        n, k = self.x.numel(), self.k
+        return float(5 * 4 * n + 8 * k + ((4 + 4 * 16) * k if self.sorted and k > 1 else 0))
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gkeys_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        rep["k"] = self.k
+        return rep
+
+    def check(self, reduce: bool = True):
+        """The outputs of the timed step against the first k entries of torch.sort(stable=True), exactly (sorted=False:
+        those entries re-ordered by index; values bit for bit: the generated keys hold no NaN and no -0.0), and the
+        look-back error word of the stream. Local only."""
+        lookback_ok = True
+        if self.x.is_cuda:
+            try:
+                ops.scan_check(self.x.device)
+            except RuntimeError:
+                lookback_ok = False
+        ref = torch.sort(self.x, stable=True, descending=self.largest)
+        rv, ri = ref.values[:self.k], ref.indices[:self.k]
+        if not self.sorted:
+            ri, o = torch.sort(ri)
+            rv = rv[o]
+        same = self.out[1].dtype == torch.int32 and torch.equal(self.out[1], ri.int()) \
+            and torch.equal(self.out[0].view(torch.int32), rv.view(torch.int32))
+        ok = bool(same)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+            lookback_ok = self.ctx.max_over_ranks(0.0 if lookback_ok else 1.0) == 0.0
+        return {"elements_checked": self.x.numel(), "k": self.k, "exact_vs_torch": ok, "lookback_ok": lookback_ok,
+                "check_passed": ok and lookback_ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
-             "sort": Sort, "segreduce": SegReduce}
+             "sort": Sort, "segreduce": SegReduce, "topk": TopK}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

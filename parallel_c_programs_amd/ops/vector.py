@@ -320,6 +320,90 @@ def sort_by_key(keys: torch.Tensor, values: torch.Tensor, descending: bool = Fal
     return _canonical_f32(kf[order]), vbits.view(values.dtype)
 
 
+# ---------------------------------------------------------------- top-k / k-th value (radix select)
+# The k best elements of the flattened input and the k-th value, in sort's order (above) and DEFINED by it:
+#     topk(x, k, largest) == tuple(t[:k] for t in sort(x, descending=largest)), bit for bit.
+# On the GPU nothing is sorted but the k survivors (csrc/kernels/topk.hip; no counterpart in the reference programs):
+# a most-significant-digit radix select finds the k-th key from four histogram passes over the keys (reads, no writes,
+# the digit chosen on the device, no inter-block waiting), one pass on the scan's decoupled look-back gathers the k
+# survivors in index order, and the stable pair sort orders them. Nothing synchronises with the host; the output size
+# is k, known on the host, so there is no exact-size form; a look-back that gave up is reported by scan_check().
+#  * Indices are int32 flat indices. Among elements that tie with the k-th key the LOWEST flat indices are taken, and
+#    ties come out in ascending index order. This is stricter than torch.topk, which leaves the choice among ties open.
+#  * float32 values come out canonical, as from sort_keys: +0.0 for both zeros, bits 0x7fffffff for every NaN. NaNs are
+#    the largest keys: they lead for largest=True.
+#  * sorted=False: the same k elements in ascending flat-index order (no survivor sort runs).
+#  * method (tests and the lab): "select" runs the radix-select kernels, "sort" runs sort and slices, None picks by the
+#    measured rule: the sort route when sorted and k > TOPK_SORT_FRACTION * numel, select otherwise (sorted=False is
+#    select for every k: 5.6x to 12x faster than sort, slice and re-order at every measured k).
+#  * Measured on one MI355X at 2^28 keys, uniform / all equal / already sorted, largest=True
+#    (profiles/r10_topk/README.md): select is 4.1x-13.4x faster than torch.topk and 4.4x-12.2x faster than sort and
+#    slice for k <= 2^24, and 1.26x-2.0x / 1.4x-1.6x at k = numel / 2 with sorted=True. The survivor sort grows with
+#    k: on uniform keys select is level with sort and slice at k = 3/4 numel (f32 9.88 against 10.07 ms, i32 9.50
+#    against 9.94) and slower at 7/8 numel (f32 11.14 against 10.09 ms, i32 10.64 against 9.95), hence the constant.
+#    method="select" on float32 with sorted=True and k >= 7/8 numel is SLOWER than torch.topk (11.14 against 10.86 ms
+#    at 7/8 numel, 12.72 against 11.03 ms at k = numel); the default rule takes the sort route there (10.09 ms). The
+#    sort route inherits sort's standing on float32: on all-equal keys it is slower than torch.topk (9.49 against
+#    8.52 ms at k = numel / 2).
+TOPK_SORT_FRACTION = 0.75
+_TOPK_METHODS = (None, "select", "sort")
+
+
+def _check_topk(x: torch.Tensor, k, k_min: int, name: str) -> None:
+    if x.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name}: x must be float32 or int32, got {x.dtype}")
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"{name}: k must be an int, got {type(k).__name__}")
+    if x.numel() > SORT_MAX_N:
+        raise ValueError(f"{name}: x has {x.numel()} elements; indices and digit counts are 30-bit (at most 2^30 - 1)")
+    if not k_min <= k <= x.numel():
+        raise ValueError(f"{name}: k must be in {k_min}..{x.numel()} (the number of elements), got {k}")
+
+
+def topk(x: torch.Tensor, k: int, largest: bool = True, sorted: bool = True, method: str | None = None):
+    """(values, indices): the k largest (or smallest) elements of x.flatten() (float32 or int32, at most SORT_MAX_N
+    elements, never written) and their int32 flat indices; exactly the first k entries of sort(x, descending=largest).
+    Stricter than torch.topk, which leaves the choice among ties open: elements that tie with the k-th key are taken by
+    lowest flat index and ties come out in ascending index order. float32 zeros and NaNs come out canonical (+0.0, bits
+    0x7fffffff); NaNs are the largest. sorted=False gives the same k elements in ascending index order. 0 <= k <=
+    x.numel(), a Python int. Does not synchronise; scan_check() reports a look-back that gave up. method: "select" (the
+    radix-select kernels), "sort" (sort and slice) or None: sort and slice when sorted and k > TOPK_SORT_FRACTION *
+    numel (0.75: on an MI355X at 2^28 uniform keys select is level there, f32 9.88 against 10.07 ms, and slower at 7/8
+    numel, 11.14 against 10.09 ms), select otherwise. At 2^28 keys select is 4.1x-13.4x faster than torch.topk for k <=
+    2^24 (f32 k = 1024: 1.53 against 9.72 ms) and 1.26x-2.0x at numel / 2; method="select" with sorted=True on float32
+    is slower than torch.topk from k = 7/8 numel (11.14 against 10.86 ms; 12.72 against 11.03 ms at k = numel), where
+    the default rule takes the sort route (10.09 ms)."""
+    _check_topk(x, k, 0, "topk")
+    if method not in _TOPK_METHODS:
+        raise ValueError(f"topk: method must be one of {_TOPK_METHODS}, got {method!r}")
+    largest, n = bool(largest), x.numel()
+    if not x.is_cuda:
+        xf = x.reshape(-1)
+        order = torch.sort(xf, stable=True, descending=largest).indices[:k]
+        if not sorted:
+            order = torch.sort(order).values
+        return _canonical_f32(xf[order]), order.int()
+    if method is None:
+        method = "sort" if sorted and k > TOPK_SORT_FRACTION * n else "select"
+    if method == "select":
+        return tuple(ops().topk(x, k, largest, bool(sorted)))
+    v, i = (t[:k] for t in ops().sort_index(x, largest, 0, 32, True))
+    if not sorted and k > 1:
+        i, v = ops().sort_pairs(i, v, False, 0, 32)  # back to index order: indices are distinct, the values ride along
+    return v, i
+
+
+def kth_value(x: torch.Tensor, k: int, largest: bool = False) -> torch.Tensor:
+    """The k-th smallest (largest=True: k-th largest) element of x.flatten() as a 0-d tensor on x's device: 1-based
+    like torch.kthvalue, equal to sort_keys(x, descending=largest)[k - 1] (float32 canonical). On the GPU the
+    threshold of the radix-select passes alone: four read passes, nothing moved, no host synchronisation."""
+    _check_topk(x, k, 1, "kth_value")
+    if x.is_cuda:
+        return ops().kth_value(x, k, bool(largest))
+    xf = x.reshape(-1)
+    return _canonical_f32(xf[torch.sort(xf, stable=True, descending=bool(largest)).indices[k - 1:k]]).reshape(())
+
+
 # ---------------------------------------------------------------- run-length encode / reduce by key / unique
 # Collapse runs of equal neighbouring keys of the flattened input and reduce a value stream per run. On the GPU one
 # pass on the scan's decoupled look-back carrying the exact integer count of run heads, a segmented reduction inside
