@@ -174,6 +174,32 @@ int pcmx_reduce_by_key_f32(const void* keys, const float* vals, long long n, int
 int pcmx_reduce_by_key_i32(const void* keys, const int32_t* vals, long long n, int op, void* run_keys, int32_t* agg,
                            long long* num_runs_dev, void* workspace, unsigned* err_flag, hipStream_t s);
 
+/* ---------------------------------------------------------------- scan by key (segmented prefix scan) */
+/* The running aggregate inside every run of a length-n stream: out[i] = op over vals[s .. i] (inclusive) or
+ * vals[s .. i-1] (exclusive != 0), s the first element of i's run (csrc/kernels/scanbykey.hip). The runs come from
+ * keys_or_heads: with PCMX_HEADS_FROM_KEYS it holds n 32-bit keys and a run is a maximal block of equal neighbours,
+ * compared as BIT PATTERNS exactly as for pcmx_reduce_by_key_* (-0.0 != +0.0, NaNs equal only with equal bits); with
+ * PCMX_HEADS_FROM_FLAGS it holds n bytes and a non-zero byte starts a run. Element 0 starts a run in either mode,
+ * whatever its flag says. op is PCMX_OP_SUM / MIN / MAX. In exclusive mode the first element of every run gets the
+ * identity: +0.0 / 0 for SUM, +inf / INT32_MAX for MIN, -inf / INT32_MIN for MAX. int32 sums wrap mod 2^32 and int32
+ * results are exact; float32 min / max are exact and hand on a NaN value to the end of its run only; a float32 sum
+ * uses a fixed association order (not input order), so the same input gives the same bits on every call, and a NaN
+ * or inf in one run never reaches another run. Three launches on the stream (tile scan with every output written,
+ * one-block scan of the tile summaries, carry added to the lead of every tile that continues a run); no block waits
+ * for another, so nothing can time out and there is no err_flag. out may be vals itself (in place); it must not
+ * overlap keys_or_heads. keys, vals, out and the workspace (pcmx_scanbykey_workspace_bytes, one call in flight per
+ * workspace) 16-B aligned, the flag bytes 4-B aligned, 0 < n < 2^31, a valid op and head mode, no NULL pointer (else
+ * PCMX_ERR_ARG, nothing launched); n <= 0 returns 0 and touches nothing. */
+enum { PCMX_HEADS_FROM_KEYS = 0, PCMX_HEADS_FROM_FLAGS = 1 };
+long long pcmx_scanbykey_workspace_bytes(long long n);
+int pcmx_scan_by_key_f32(const void* keys_or_heads, int head_mode, const float* vals, float* out, long long n, int op,
+                         int exclusive, void* workspace, hipStream_t s);
+int pcmx_scan_by_key_i32(const void* keys_or_heads, int head_mode, const int32_t* vals, int32_t* out, long long n, int op,
+                         int exclusive, void* workspace, hipStream_t s);
+/* out[i] = int32 index of element i inside its run (0, 1, 2, ...): the exclusive sum-scan by key of the constant 1;
+ * no value stream is read */
+int pcmx_run_positions_b32(const void* keys, int32_t* out, long long n, void* workspace, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

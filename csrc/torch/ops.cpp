@@ -510,6 +510,84 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> reduce_by_key(const at::Tensor& k
     return {rk, ra, count};
 }
 
+// ---------------------------------------------------------------- scan by key (segmented prefix scan)
+// The running aggregate inside every run (csrc/kernels/scanbykey.hip): the result has the values' dtype and shape, the
+// optional caller tensor `out` (contiguous, values.numel() elements) may be the values themselves (in place). Keys or
+// head flags that overlap the output are cloned first, as reduce_by_key does. No block of these kernels waits for
+// another one, so there is no error word to share and nothing synchronises.
+bool same_elements(const at::Tensor& a, const at::Tensor& b) {
+    return a.data_ptr() == b.data_ptr() && a.numel() == b.numel() && a.element_size() == b.element_size();
+}
+
+// runs: the flat, contiguous, aligned keys (PCMX_HEADS_FROM_KEYS) or flag bytes (PCMX_HEADS_FROM_FLAGS)
+at::Tensor scan_by_key_launch(at::Tensor runs, int head_mode, const at::Tensor& values, int64_t op, bool exclusive,
+                              const c10::optional<at::Tensor>& out, const char* what) {
+    TORCH_CHECK(op >= PCMX_OP_SUM && op <= PCMX_OP_MAX, what, ": op code ", op);
+    TORCH_CHECK(values.is_cuda() && values.device() == runs.device(), what, ": values must be on the device of the keys or heads");
+    TORCH_CHECK(values.scalar_type() == at::kFloat || values.scalar_type() == at::kInt, what, ": values have dtype ",
+                values.scalar_type(), ", expected float32 or int32");
+    const int64_t n = values.numel();
+    TORCH_CHECK(n == runs.numel(), what, ": ", n, " values for ", runs.numel(), " keys or heads");
+    TORCH_CHECK(n < (1LL << 31), what, ": the values must have fewer than 2^31 elements");
+    const bool has_out = out.has_value() && out->defined();
+    if (has_out) {
+        check_gpu(*out, "out", values.scalar_type());
+        TORCH_CHECK(out->device() == values.device() && out->is_contiguous() && out->numel() == n, what,
+                    ": out must be contiguous, on the values' device, with ", n, " elements");
+    }
+    if (n == 0) return has_out ? *out : at::empty_like(values);
+    at::Tensor vc = aligned_contig(values).view(-1);
+    at::Tensor dest = has_out && !(reinterpret_cast<uintptr_t>(out->data_ptr()) & 15u) ? out->view(-1)
+                                                                                      : at::empty({n}, values.options());
+    if (overlaps(vc, dest) && !same_elements(vc, dest)) vc = vc.clone();  // identical is fine: the call is in place
+    if (overlaps(runs, dest)) runs = runs.clone();
+    hipStream_t stream = cur_stream(values);
+    auto ws = workspace(values, pcmx_scanbykey_workspace_bytes(n));
+    if (values.scalar_type() == at::kFloat)
+        check_rc(pcmx_scan_by_key_f32(runs.data_ptr(), head_mode, vc.data_ptr<float>(), dest.data_ptr<float>(), n, (int)op,
+                                      exclusive ? 1 : 0, ws.data_ptr(), stream),
+                 what);
+    else
+        check_rc(pcmx_scan_by_key_i32(runs.data_ptr(), head_mode, vc.data_ptr<int32_t>(), dest.data_ptr<int32_t>(), n,
+                                      (int)op, exclusive ? 1 : 0, ws.data_ptr(), stream),
+                 what);
+    if (has_out) {
+        if (dest.data_ptr() != out->data_ptr()) out->view(-1).copy_(dest);
+        return *out;
+    }
+    return dest.view(values.sizes());
+}
+
+at::Tensor scan_by_key(const at::Tensor& keys, const at::Tensor& values, int64_t op, bool exclusive,
+                       const c10::optional<at::Tensor>& out) {
+    sort_key_type(keys, "scan_by_key");
+    const at::DeviceGuard g(keys.device());
+    return scan_by_key_launch(aligned_contig(keys).view(-1), PCMX_HEADS_FROM_KEYS, values, op, exclusive, out, "scan_by_key");
+}
+
+at::Tensor segmented_scan(const at::Tensor& values, const at::Tensor& heads, int64_t op, bool exclusive,
+                          const c10::optional<at::Tensor>& out) {
+    TORCH_CHECK(values.is_cuda(), "segmented_scan: values must be a GPU tensor");
+    const at::DeviceGuard g(values.device());
+    TORCH_CHECK(heads.device() == values.device(), "segmented_scan: heads must be on the values' device");
+    return scan_by_key_launch(mask_bytes(heads, values.numel(), "segmented_scan"), PCMX_HEADS_FROM_FLAGS, values, op,
+                              exclusive, out, "segmented_scan");
+}
+
+at::Tensor run_positions(const at::Tensor& keys) {
+    sort_key_type(keys, "run_positions");
+    const at::DeviceGuard g(keys.device());
+    const int64_t n = keys.numel();
+    TORCH_CHECK(n < (1LL << 31), "run_positions: the keys must have fewer than 2^31 elements");
+    at::Tensor pos = at::empty(keys.sizes(), keys.options().dtype(at::kInt));
+    if (n == 0) return pos;
+    at::Tensor kc = aligned_contig(keys).view(-1);
+    auto ws = workspace(keys, pcmx_scanbykey_workspace_bytes(n));
+    check_rc(pcmx_run_positions_b32(kc.data_ptr(), pos.data_ptr<int32_t>(), n, ws.data_ptr(), cur_stream(keys)),
+             "run_positions");
+    return pos;
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -1051,6 +1129,9 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("kth_value(Tensor x, int k, bool largest=False) -> Tensor");
     m.def("run_length_encode(Tensor keys, bool starts=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_counts=None, Tensor(c!)? out_starts=None) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("reduce_by_key(Tensor keys, Tensor values, int op, Tensor(a!)? out_keys=None, Tensor(b!)? out=None) -> (Tensor, Tensor, Tensor)");
+    m.def("scan_by_key(Tensor keys, Tensor values, int op, bool exclusive=False, Tensor(a!)? out=None) -> Tensor");
+    m.def("segmented_scan(Tensor values, Tensor heads, int op, bool exclusive=False, Tensor(a!)? out=None) -> Tensor");
+    m.def("run_positions(Tensor keys) -> Tensor");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -1099,6 +1180,9 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("kth_value", kth_value);
     m.impl("run_length_encode", run_length_encode);
     m.impl("reduce_by_key", reduce_by_key);
+    m.impl("scan_by_key", scan_by_key);
+    m.impl("segmented_scan", segmented_scan);
+    m.impl("run_positions", run_positions);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

@@ -848,6 +848,159 @@ class SegReduce(Workload):
                 "lookback_ok": lookback_ok, "check_passed": ok and lookback_ok}
 
 
+class ScanByKey(Workload):
+    """The running op inside every run of n elements per GPU (csrc/kernels/scanbykey.hip): mode "keys"
+    (ops.scan_by_key on int32 keys), "heads" (ops.segmented_scan on the bool head flags of the same runs) or "positions"
+    (ops.run_positions: no values). op sum, min or max over values of dtype f32 (uniform in [0, 1)) or i32 (0..999),
+    inclusive or exclusive. The runs are SegReduce's: element i starts one when a seeded counter falls below
+    1 / mean_run (geometric lengths), mean_run=0 makes every key equal (the carry crosses every tile and the lead kernel
+    rewrites the whole output). No communication (weak scaling)."""
+
+    def __init__(self, ctx, n=1 << 28, mean_run=4.0, op="sum", dtype="f32", exclusive=False, mode="keys", **_):
+        if mode not in ("keys", "heads", "positions"):
+            raise ValueError(f"scanbykey mode {mode!r}: keys, heads or positions")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"scanbykey dtype {dtype!r}: f32 or i32")
+        if op not in ops.OP_CODES:
+            raise ValueError(f"scanbykey op {op!r}: sum, min or max")
+        if float(mean_run) < 0 or 0 < float(mean_run) < 1:
+            raise ValueError(f"scanbykey mean_run {mean_run!r}: 0 (all keys equal) or >= 1")
+        super().__init__(ctx, {"n": int(n), "mean_run": float(mean_run), "op": op, "dtype": dtype,
+                               "exclusive": bool(exclusive), "mode": mode}, "scanbykey", "GB/s")
+        n, dev, mean_run = int(n), ctx.device, float(mean_run)
+        self.mode, self.op, self.exclusive = mode, op, bool(exclusive)
+        u = ops.rand_uniform_(torch.empty(n, device=dev), 10000 + ctx.rank, 0.0, 1.0)  # the seeded counter
+        head = u < (1.0 / mean_run if mean_run else 0.0)
+        del u
+        self.heads = head if mode == "heads" else None  # heads[0] may be 0: element 0 starts a run anyway
+        self.keys = None if mode == "heads" else (torch.cumsum(head, 0) % (1 << 24)).int()  # neighbouring runs differ
+        del head
+        self.values = None
+        if mode != "positions":
+            v = ops.rand_uniform_(torch.empty(n, device=dev), 11000 + ctx.rank, 0.0, 1.0)
+            self.values = v if dtype == "f32" else (v * 1000.0).int()
+        self.out = None
+
+    def step(self):
+        if self.mode == "keys":
+            self.out = ops.scan_by_key(self.keys, self.values, self.op, self.exclusive)
+        elif self.mode == "heads":
+            self.out = ops.segmented_scan(self.values, self.heads, self.op, self.exclusive)
+        else:
+            self.out = ops.run_positions(self.keys)
+
+    def torch_step(self):
+        """The torch composition this op replaces: run indices from unique_consecutive (or a cumsum of the flags), then
+        a cumsum minus the gathered per-run base (float32 sums cancel), or a cummax over values lifted by
+        4096 * run index for min / max (values below 1000 in magnitude, as here)."""
+        if self.mode == "heads":
+            h = self.heads.clone()
+            h[:1] = True
+            inv = torch.cumsum(h, 0) - 1
+            starts = torch.nonzero(h).view(-1)
+        else:
+            _, inv, cnt = torch.unique_consecutive(self.keys, return_inverse=True, return_counts=True)
+            starts = torch.cumsum(cnt, 0) - cnt
+        if self.mode == "positions":
+            return (torch.arange(inv.numel(), device=inv.device) - starts[inv]).int()
+        v = self.values
+        if self.op == "sum":
+            c = torch.cumsum(v, 0, dtype=v.dtype)
+            r = c - (c - v)[starts][inv]
+            return r - v if self.exclusive else r
+        sign = 1 if self.op == "max" else -1
+        lift = inv.to(torch.float64 if v.dtype == torch.float32 else torch.int64) * 4096
+        r = (sign * (torch.cummax(sign * v + lift, 0).values - lift)).to(v.dtype)
+        if self.exclusive:
+            ident = _scan_identity(self.op, v.dtype)
+            r = torch.cat([r.new_full((1,), ident), r[:-1]])
+            r[starts] = ident
+        return r
+
+    def work_per_step(self):
+        # bytes moved once: keys or flag bytes, values, every output (the lead kernel's second pass is not counted)
+        n = (self.keys if self.keys is not None else self.heads).numel()
+        return float({"keys": 12, "heads": 9, "positions": 8}[self.mode] * n)
+
+    def check(self, reduce: bool = True, chunk: int = 1 << 26):
+        """Every output of the timed step against an exact oracle, chunk by chunk (a run that crosses a chunk border
+        takes the previous chunk's last inclusive value as its carry): sums as an int64 / fp64 cumsum minus the gathered
+        per-run base (int32 wrapped and compared exactly, float32 to REL_ERR_LIMIT of the fp64 value), min / max and
+        positions exactly (a cummax over order-preserving int64 keys lifted by 2^33 * run index, so later runs
+        dominate). Local only."""
+        src = self.keys.view(torch.int32) if self.keys is not None else self.heads
+        n, dev = src.numel(), src.device
+        got_all = self.out.reshape(-1)
+        same, carry, runs = True, None, 0
+        is_f32 = self.mode != "positions" and self.values.dtype == torch.float32
+        for s in range(0, n, chunk):
+            e = min(n, s + chunk)
+            m = e - s
+            head = torch.ones(m, dtype=torch.bool, device=dev)
+            if self.keys is not None:
+                head[1:] = src[s + 1:e] != src[s:e - 1]
+                joins = bool(s > 0 and (src[s] == src[s - 1]).item())
+            else:
+                head[1:] = src[s + 1:e] != 0
+                joins = bool(s > 0 and (src[s] == 0).item())
+            idx = torch.arange(m, device=dev)
+            start = torch.cummax(torch.where(head, idx, 0), 0).values
+            inv = torch.cumsum(head, 0) - 1
+            runs += int(inv[-1].item()) + (0 if joins else 1)
+            lead = (inv == 0) if joins else torch.zeros(m, dtype=torch.bool, device=dev)
+            got = got_all[s:e]
+            if self.mode == "positions":
+                ref = idx - start
+                if joins:
+                    ref = ref + lead * carry
+                carry = ref[-1] + 1
+                same = same and torch.equal(got.long(), ref)
+            elif self.op == "sum":
+                acc = torch.float64 if is_f32 else torch.int64
+                v = self.values[s:e].to(acc)
+                c = torch.cumsum(v, 0)
+                ref = c - (c - v)[start]
+                if joins:
+                    ref = ref + lead * carry
+                carry = ref[-1]
+                if self.exclusive:
+                    ref = ref - v
+                if is_f32:
+                    same = same and bool(((got.double() - ref).abs() <= REL_ERR_LIMIT * ref.abs().clamp_min(1.0)).all())
+                else:
+                    same = same and torch.equal(got.long(), ((ref + (1 << 31)) % (1 << 32)) - (1 << 31))
+            else:
+                sign = 1 if self.op == "max" else -1
+                ident = _ordered_i64(torch.full((1,), _scan_identity(self.op, got.dtype), dtype=got.dtype, device=dev))
+                lift = inv << 33
+                ref = sign * (torch.cummax(sign * _ordered_i64(self.values[s:e]) + lift, 0).values - lift)
+                if joins:
+                    ref = torch.where(lead, torch.maximum(sign * ref, sign * carry) * sign, ref)
+                prev, carry = carry, ref[-1:].clone()
+                if self.exclusive:
+                    ref = torch.cat([prev if joins else ident, ref[:-1]])
+                    ref[1:] = torch.where(head[1:], ident, ref[1:])
+                same = same and torch.equal(_ordered_i64(got), ref)
+        ok = bool(same)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"runs": runs, "elements_checked": n, "matches_oracle": ok, "check_passed": ok}
+
+
+def _scan_identity(op: str, dtype: torch.dtype):
+    if dtype == torch.float32:
+        return {"sum": 0.0, "min": float("inf"), "max": float("-inf")}[op]
+    return {"sum": 0, "min": 2**31 - 1, "max": -2**31}[op]
+
+
+def _ordered_i64(t: torch.Tensor) -> torch.Tensor:
+    """int64 keys in the order of the values of an int32 or NaN-free float32 tensor (the two zeros share a key)."""
+    if t.dtype != torch.float32:
+        return t.long()
+    b = t.contiguous().view(torch.int32).long()
+    return torch.where(b >= 0, b, -(b & 0x7fffffff))
+
+
 class TopK(Workload):
     """The k best of n keys per GPU and their indices (csrc/kernels/topk.hip): dtype f32 (uniform in [-1, 1)) or i32
     (uniform over the full range); dist "equal" makes every key the same (every key ties with the k-th: the gather
@@ -924,7 +1077,7 @@ class TopK(Workload):
 
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
-             "sort": Sort, "segreduce": SegReduce, "topk": TopK}
+             "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

@@ -6,8 +6,9 @@ from .image import (SEED_3D, Camera, apply_region_mask, corner_seeds, create_vol
 from .sparse import CSR, SlicedCSR, banded_csr, create_vector, powerlaw_csr, spmv, spmv_banded
 from .stencil import init_grid, stencil5_reference, stencil5_step_, stencil5x2_step_, stencil5_fused_step_, stencil5_fused_spans_
 from .vector import (CMP_CODES, OP_CODES, argsort, axpy_, compact, compact_indices, compact_where, copy_, dot, fill_,
-                     gather_, kth_value, rand_uniform_, reduce, reduce_by_key, run_length_encode, scan, scan_check, select,
-                     select_indices, sort, sort_by_key, sort_keys, sum_by_key, topk, unique, unique_consecutive, vadd, vmul)
+                     gather_, kth_value, rand_uniform_, reduce, reduce_by_key, run_length_encode, run_positions, scan,
+                     scan_by_key, scan_check, segmented_scan, select, select_indices, sort, sort_by_key, sort_keys, sum_by_key,
+                     topk, unique, unique_consecutive, vadd, vmul)
 
 __all__ = [
     "sgemm", "sgemm_out", "sgemm_simt", "sgemm_naive_host",
@@ -20,4 +21,5 @@ __all__ = [
     "compact", "select", "compact_indices", "select_indices", "compact_where", "CMP_CODES",
     "sort_keys", "sort", "argsort", "sort_by_key", "topk", "kth_value",
     "run_length_encode", "reduce_by_key", "unique_consecutive", "unique", "sum_by_key",
+    "scan_by_key", "segmented_scan", "run_positions",
 ]

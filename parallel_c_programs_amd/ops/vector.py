@@ -533,3 +533,136 @@ def sum_by_key(keys: torch.Tensor, values: torch.Tensor):
     rk, ra, num = reduce_by_key(ks, vs, "sum")
     k = int(num.item())
     return rk[:k], ra[:k]
+
+
+# ---------------------------------------------------------------- scan by key (segmented prefix scan)
+# The running aggregate INSIDE every run, where reduce_by_key gives one aggregate per run: out[i] = op(values[s..i])
+# (inclusive) or op(values[s..i-1]) (exclusive), s the first element of i's run. The runs are those of the KEY RULE
+# above (scan_by_key, run_positions) or start at the non-zero entries of a bool / uint8 tensor (segmented_scan);
+# element 0 always starts one. On the GPU three launches with no waiting between blocks (csrc/kernels/scanbykey.hip):
+# every 32768-element tile is scanned and written with the identity as carry-in, one block scans the tile summaries in
+# a fixed order, and the carry is combined into the lead of every tile that continues a run.
+#  * The result has the values' dtype and shape; `out` (contiguous, same numel and dtype) may be the values tensor
+#    itself (in place); keys or heads that overlap out are cloned first. Nothing synchronises; n == 0 launches nothing.
+#  * Exclusive mode gives the first element of every run the identity: +0.0 / 0 for sum, +inf / INT32_MAX for min,
+#    -inf / INT32_MIN for max.
+#  * int32 sums wrap mod 2^32 and int32 results are exact; float32 min / max are exact and hand on a NaN to the end
+#    of that run only; a float32 sum uses a fixed association order (not input order): the same input gives the same
+#    bits on every call. A NaN or inf in one run never reaches another run.
+#  * Measured against the torch composition (unique_consecutive + cumsum minus the gathered per-run base) on one
+#    MI355X at 2^28 int32 keys, mean run length 1 to 10^5 and all equal (profiles/r11_scanbykey/README.md): sums
+#    14.2x-4.7x faster (0.61-1.02 ms), run_positions 16.9x-5.7x (0.50-0.92 ms); the slow end is all keys equal, where
+#    the lead of every tile is the whole tile and the output is written twice.
+_SCAN_IDENTITY = {"sum": (0.0, 0), "min": (float("inf"), 2**31 - 1), "max": (float("-inf"), -2**31)}
+_SCAN_COMBINE = {"sum": torch.add, "min": torch.minimum, "max": torch.maximum}
+
+
+def _check_scan_out(out: torch.Tensor | None, values: torch.Tensor) -> None:
+    if out is None:
+        return
+    if out.dtype != values.dtype:
+        raise TypeError(f"out must be {values.dtype}, got {out.dtype}")
+    if out.device != values.device:
+        raise ValueError(f"out is on {out.device}, the values on {values.device}")
+    if not out.is_contiguous() or out.numel() != values.numel():
+        raise ValueError(f"out must be contiguous with the values' {values.numel()} elements, got shape "
+                         f"{tuple(out.shape)}")
+
+
+def _host_segmented_scan(head: torch.Tensor, values: torch.Tensor, op: str, exclusive: bool,
+                         out: torch.Tensor | None) -> torch.Tensor:
+    """The CPU path of the three ops: head is a flat bool tensor with head[0] set. Integer sums through an int64 cumsum
+    (exact, wrapped); everything else by doubling steps inside the runs (x[i] = op(x[i - d], x[i]) while i - d is in
+    i's run, d = 1, 2, 4, ...), which keeps a NaN or inf inside its run and is a fixed order for float32 sums."""
+    v = values.reshape(-1)
+    n = v.numel()
+    if n == 0:
+        return out if out is not None else torch.empty_like(values)
+    pos = torch.arange(n) - torch.cummax(torch.where(head, torch.arange(n), 0), 0).values  # index inside the run
+    ident = _SCAN_IDENTITY[op][0 if v.dtype == torch.float32 else 1]
+    if op == "sum" and v.dtype == torch.int32:
+        c = torch.cumsum(v.long(), 0)
+        incl = c - (c - v)[torch.arange(n) - pos]
+        incl = (((incl + (1 << 31)) % (1 << 32)) - (1 << 31)).int()
+    else:
+        incl, d, longest = v.clone(), 1, int(pos.max())
+        while d <= longest:
+            joined = _SCAN_COMBINE[op](incl[:-d], incl[d:])
+            incl[d:] = torch.where(pos[d:] >= d, joined, incl[d:])
+            d *= 2
+    res = incl
+    if exclusive:
+        res = torch.full_like(incl, ident)
+        res[1:] = torch.where(head[1:], res[1:], incl[:-1])
+    if out is None:
+        return res.reshape(values.shape)
+    out.view(-1).copy_(res)
+    return out
+
+
+def _check_scan_op(op: str) -> None:
+    if op not in OP_CODES:
+        raise ValueError(f"op must be one of {sorted(OP_CODES)}, got {op!r}")
+
+
+def _key_heads(keys: torch.Tensor) -> torch.Tensor:
+    bits = keys.reshape(-1).contiguous().view(torch.int32)
+    head = torch.ones(bits.numel(), dtype=torch.bool)
+    head[1:] = bits[1:] != bits[:-1]
+    return head
+
+
+def scan_by_key(keys: torch.Tensor, values: torch.Tensor, op: str = "sum", exclusive: bool = False,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """The running op (sum, min, max) of values (float32 or int32) inside every run of equal neighbouring keys of
+    keys.flatten() (float32 or int32, same numel, compared as bit patterns: -0.0 != +0.0, NaNs equal only with equal
+    bits), with the values' dtype and shape: out[i] = op(values[s..i]), or op(values[s..i-1]) when exclusive (the first
+    element of a run then gets the identity: 0, +inf / INT32_MAX, -inf / INT32_MIN), s the first element of i's run.
+    int32 sums wrap mod 2^32; int32 results are exact; float32 min / max are exact and hand on a NaN to the end of its
+    run only; a float32 sum uses a fixed association order (not input order): the same input gives the same bits on
+    every call. out (contiguous, same dtype and numel) may be values itself. Does not synchronise."""
+    _check_seg_keys(keys)
+    _check_scan_op(op)
+    _check_seg_values(keys, values)
+    _check_scan_out(out, values)
+    if keys.is_cuda:
+        return ops().scan_by_key(keys, values, OP_CODES[op], bool(exclusive), out)
+    return _host_segmented_scan(_key_heads(keys), values, op, bool(exclusive), out)
+
+
+def segmented_scan(values: torch.Tensor, heads: torch.Tensor, op: str = "sum", exclusive: bool = False,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """scan_by_key with the runs given by flags: a non-zero entry of heads.flatten() (bool or uint8, same numel) starts
+    a run, and element 0 starts one whatever heads[0] says. segmented_scan(v, h) equals scan_by_key(k, v) when h[i] =
+    (bits of k[i] != bits of k[i-1])."""
+    if values.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"values must be float32 or int32, got {values.dtype}")
+    if values.numel() >= 1 << 31:
+        raise ValueError(f"values have {values.numel()} elements; tile offsets are int32 (fewer than 2^31)")
+    if heads.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"heads must be bool or uint8, got {heads.dtype}")
+    if heads.numel() != values.numel():
+        raise ValueError(f"{heads.numel()} heads for {values.numel()} values")
+    if heads.device != values.device:
+        raise ValueError(f"heads are on {heads.device}, the values on {values.device}")
+    _check_scan_op(op)
+    _check_scan_out(out, values)
+    if values.is_cuda:
+        return ops().segmented_scan(values, heads, OP_CODES[op], bool(exclusive), out)
+    head = heads.reshape(-1) != 0
+    if head.numel():
+        head[0] = True
+    return _host_segmented_scan(head, values, op, bool(exclusive), out)
+
+
+def run_positions(keys: torch.Tensor) -> torch.Tensor:
+    """int32 index of every element inside its run of equal neighbouring keys (0, 1, 2, ... from each run's first
+    element), with the keys' shape: the exclusive sum-scan by key of the constant 1; no value stream is read. Keys as
+    in scan_by_key. Does not synchronise."""
+    _check_seg_keys(keys)
+    if keys.is_cuda:
+        return ops().run_positions(keys)
+    n = keys.numel()
+    head = _key_heads(keys)
+    start = torch.cummax(torch.where(head, torch.arange(n), 0), 0).values if n else torch.arange(0)
+    return (torch.arange(n) - start).int().reshape(keys.shape)
