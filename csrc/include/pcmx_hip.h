@@ -200,6 +200,35 @@ int pcmx_scan_by_key_i32(const void* keys_or_heads, int head_mode, const int32_t
  * no value stream is read */
 int pcmx_run_positions_b32(const void* keys, int32_t* out, long long n, void* workspace, hipStream_t s);
 
+/* ---------------------------------------------------------------- histograms (bincount / even bins / explicit edges) */
+/* Counts of a length-n sample stream in out[0 .. num_bins) (int32; csrc/kernels/bincount.hip). A sample that falls in
+ * no bin is ignored: never an error, never an access outside out. accumulate == 0 zeroes out first (on the stream),
+ * accumulate != 0 adds to what it holds. The samples are never written. One persistent kernel, no block waits for
+ * another, the only traffic between blocks is integer atomic adds: counts are exact and the same on every call; there
+ * is no workspace and no err_flag. Up to 24576 bins are counted in LDS per block and merged at the end; up to 64 * 24576
+ * bins (bincount_i32 and hist_even) the blocks share the bins out in ranges and each reads its input slice for its
+ * range; more bins are added straight into out.
+ *  bincount: the bin of a sample is its value; values < 0 or >= num_bins are ignored. weights (may be NULL) are n
+ *   int32 values: out[b] += weights[i] instead of 1, sums wrap mod 2^32.
+ *  hist_even: bin = min((int)((v - lo) * scale), num_bins - 1) in float32 with each step rounded separately, counted
+ *   only when lo <= v <= hi (compared in float before any conversion: NaN and +-inf are ignored). The caller passes
+ *   scale = (float)num_bins / (hi - lo), computed once in float32.
+ *  hist_range: edges holds num_bins + 1 ascending float32 values in device memory, 1 <= num_bins <= 8192; bin i holds
+ *   edges[i] <= v < edges[i+1], the last bin also v == edges[num_bins]; NaN and values outside are ignored. Edges that
+ *   do not ascend give unspecified counts, but every index is clamped: nothing outside out or edges is touched.
+ * Alignment: x to its element size (any element-aligned start works: the kernel peels the bytes before the first and
+ * after the last whole 16-byte vector), out and edges 4-B; with weights, x and weights both 16-B. 1 <= num_bins < 2^31,
+ * n < 2^31, lo < hi and a finite scale >= 0 (else PCMX_ERR_ARG, nothing launched); n <= 0 only zeroes out (or leaves
+ * it, when accumulating). */
+int pcmx_bincount_i32(const int32_t* x, const int32_t* weights, long long n, long long num_bins, int32_t* out,
+                      int accumulate, hipStream_t s);
+int pcmx_bincount_u8(const unsigned char* x, const int32_t* weights, long long n, long long num_bins, int32_t* out,
+                     int accumulate, hipStream_t s);
+int pcmx_hist_even_f32(const float* x, long long n, long long num_bins, float lo, float hi, float scale, int32_t* out,
+                       int accumulate, hipStream_t s);
+int pcmx_hist_range_f32(const float* x, long long n, const float* edges, long long num_bins, int32_t* out,
+                        int accumulate, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

@@ -588,6 +588,96 @@ at::Tensor run_positions(const at::Tensor& keys) {
     return pos;
 }
 
+// ---------------------------------------------------------------- histograms (bincount / even bins / explicit edges)
+// int32 counts of the flattened samples (csrc/kernels/bincount.hip). The samples keep their element-aligned start (a
+// view such as x[1:] is not copied; the kernel peels its ends); only a non-contiguous input is gathered first. `out`
+// is a 1-D int32 tensor of num_bins entries; accumulate adds into it instead of zeroing it. No workspace, no sync.
+struct HistDest {
+    at::Tensor dest;  // contiguous int32 [num_bins]: the caller's out where it is contiguous
+    bool copy_back;
+};
+
+HistDest hist_dest(const at::Tensor& x, int64_t num_bins, const c10::optional<at::Tensor>& out, bool accumulate,
+                   const char* what) {
+    TORCH_CHECK(num_bins >= 1 && num_bins < (1LL << 31), what, ": ", num_bins, " bins (1 to 2^31 - 1)");
+    TORCH_CHECK(x.numel() < (1LL << 31), what, ": the samples must have fewer than 2^31 elements");
+    const bool has_out = out.has_value() && out->defined();
+    TORCH_CHECK(has_out || !accumulate, what, ": accumulate needs out");
+    if (!has_out) return {at::empty({num_bins}, x.options().dtype(at::kInt)), false};
+    check_gpu(*out, "out", at::kInt);
+    TORCH_CHECK(out->device() == x.device() && out->dim() == 1 && out->numel() == num_bins, what,
+                ": out must be 1-D, on the samples' device, with ", num_bins, " entries");
+    if (out->is_contiguous()) return {*out, false};
+    return {accumulate ? out->contiguous() : at::empty({num_bins}, out->options()), true};
+}
+
+at::Tensor hist_finish(const HistDest& d, const c10::optional<at::Tensor>& out) {
+    if (!d.copy_back) return d.dest;
+    out->copy_(d.dest);
+    return *out;
+}
+
+at::Tensor bincount(const at::Tensor& x, int64_t num_bins, const c10::optional<at::Tensor>& weights,
+                    const c10::optional<at::Tensor>& out, bool accumulate) {
+    TORCH_CHECK(x.is_cuda(), "bincount: x must be a GPU tensor");
+    TORCH_CHECK(x.scalar_type() == at::kInt || x.scalar_type() == at::kByte, "bincount: x has dtype ", x.scalar_type(),
+                ", expected int32 or uint8");
+    const at::DeviceGuard g(x.device());
+    HistDest d = hist_dest(x, num_bins, out, accumulate, "bincount");
+    const bool has_w = weights.has_value() && weights->defined();
+    at::Tensor xc = x.contiguous().view(-1), wc;
+    if (has_w) {
+        check_gpu(*weights, "weights", at::kInt);
+        TORCH_CHECK(weights->device() == x.device() && weights->numel() == x.numel(), "bincount: ", weights->numel(),
+                    " weights for ", x.numel(), " samples on ", x.device());
+        xc = aligned_contig(xc), wc = aligned_contig(*weights).view(-1);
+        if (overlaps(wc, d.dest)) wc = wc.clone();
+    }
+    if (overlaps(xc, d.dest)) xc = xc.clone();
+    const int32_t* w = has_w ? wc.data_ptr<int32_t>() : nullptr;
+    const int acc = accumulate ? 1 : 0;
+    if (x.scalar_type() == at::kInt)
+        check_rc(pcmx_bincount_i32(xc.data_ptr<int32_t>(), w, xc.numel(), num_bins, d.dest.data_ptr<int32_t>(), acc,
+                                   cur_stream(x)),
+                 "bincount");
+    else
+        check_rc(pcmx_bincount_u8(xc.data_ptr<uint8_t>(), w, xc.numel(), num_bins, d.dest.data_ptr<int32_t>(), acc,
+                                  cur_stream(x)),
+                 "bincount");
+    return hist_finish(d, out);
+}
+
+// scale = float32(bins) / (float32(hi) - float32(lo)), computed once by the caller
+at::Tensor hist_even(const at::Tensor& x, int64_t bins, double lo, double hi, double scale,
+                     const c10::optional<at::Tensor>& out, bool accumulate) {
+    check_gpu(x, "x", at::kFloat);
+    const at::DeviceGuard g(x.device());
+    HistDest d = hist_dest(x, bins, out, accumulate, "hist_even");
+    at::Tensor xc = x.contiguous().view(-1);
+    if (overlaps(xc, d.dest)) xc = xc.clone();
+    check_rc(pcmx_hist_even_f32(xc.data_ptr<float>(), xc.numel(), bins, (float)lo, (float)hi, (float)scale,
+                                d.dest.data_ptr<int32_t>(), accumulate ? 1 : 0, cur_stream(x)),
+             "hist_even");
+    return hist_finish(d, out);
+}
+
+at::Tensor hist_range(const at::Tensor& x, const at::Tensor& edges, const c10::optional<at::Tensor>& out,
+                      bool accumulate) {
+    check_gpu(x, "x", at::kFloat), check_gpu(edges, "edges", at::kFloat);
+    TORCH_CHECK(edges.device() == x.device() && edges.dim() == 1 && edges.numel() >= 2, "hist_range: edges must be 1-D, on the "
+                "samples' device, with at least 2 values");
+    const at::DeviceGuard g(x.device());
+    const int64_t bins = edges.numel() - 1;
+    HistDest d = hist_dest(x, bins, out, accumulate, "hist_range");
+    at::Tensor xc = x.contiguous().view(-1), ec = edges.contiguous();
+    if (overlaps(xc, d.dest)) xc = xc.clone();
+    if (overlaps(ec, d.dest)) ec = ec.clone();
+    check_rc(pcmx_hist_range_f32(xc.data_ptr<float>(), xc.numel(), ec.data_ptr<float>(), bins, d.dest.data_ptr<int32_t>(),
+                                 accumulate ? 1 : 0, cur_stream(x)),
+             "hist_range (at most 8192 bins)");
+    return hist_finish(d, out);
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -1132,6 +1222,9 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("scan_by_key(Tensor keys, Tensor values, int op, bool exclusive=False, Tensor(a!)? out=None) -> Tensor");
     m.def("segmented_scan(Tensor values, Tensor heads, int op, bool exclusive=False, Tensor(a!)? out=None) -> Tensor");
     m.def("run_positions(Tensor keys) -> Tensor");
+    m.def("bincount(Tensor x, int num_bins, Tensor? weights=None, Tensor(a!)? out=None, bool accumulate=False) -> Tensor");
+    m.def("hist_even(Tensor x, int bins, float lo, float hi, float scale, Tensor(a!)? out=None, bool accumulate=False) -> Tensor");
+    m.def("hist_range(Tensor x, Tensor edges, Tensor(a!)? out=None, bool accumulate=False) -> Tensor");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -1183,6 +1276,9 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("scan_by_key", scan_by_key);
     m.impl("segmented_scan", segmented_scan);
     m.impl("run_positions", run_positions);
+    m.impl("bincount", bincount);
+    m.impl("hist_even", hist_even);
+    m.impl("hist_range", hist_range);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

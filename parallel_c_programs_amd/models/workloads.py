@@ -1075,9 +1075,123 @@ class TopK(Workload):
                 "check_passed": ok and lookback_ok}
 
 
+class Bincount(Workload):
+    """int32 counts of n samples per GPU in num_bins bins (csrc/kernels/bincount.hip): mode "bincount" (ops.bincount on
+    i32 or u8 samples, weights none, i32 or f32), "histc" (ops.histc on f32 samples over [0, 1]) or "edges"
+    (ops.histogram with num_bins + 1 evenly spaced edges over [0, 1], at most 8192 bins). dist: "uniform" over the
+    bins, "equal" (every sample in the middle bin: the worst case for same-address atomics), "sorted" (uniform, then
+    sorted ascending) or "zipf" (bin b with weight about 1 / (b + 1)). f32 samples sit at bin centres. u8 samples reach
+    at most 256 bins. No communication (weak scaling)."""
+
+    def __init__(self, ctx, n=1 << 28, num_bins=256, dist="uniform", dtype="i32", mode="bincount", weights="none", **_):
+        if dist not in ("uniform", "equal", "sorted", "zipf"):
+            raise ValueError(f"bincount dist {dist!r}: uniform, equal, sorted or zipf")
+        if dtype not in ("i32", "u8", "f32") or mode not in ("bincount", "histc", "edges"):
+            raise ValueError(f"bincount dtype {dtype!r} / mode {mode!r}: i32, u8 or f32 / bincount, histc or edges")
+        if (mode == "bincount") == (dtype == "f32"):
+            raise ValueError(f"bincount mode {mode!r} takes {'i32 or u8' if mode == 'bincount' else 'f32'} samples")
+        if weights not in ("none", "i32", "f32") or (weights != "none" and mode != "bincount"):
+            raise ValueError(f"bincount weights {weights!r}: none, i32 or f32, with mode bincount only")
+        n, num_bins, dev = int(n), int(num_bins), ctx.device
+        if num_bins < 1 or (mode == "edges" and num_bins > ops.vector.HIST_MAX_EDGE_BINS):
+            raise ValueError(f"bincount num_bins {num_bins}: at least 1, at most 8192 in mode edges")
+        super().__init__(ctx, {"n": n, "num_bins": num_bins, "dist": dist, "dtype": dtype, "mode": mode,
+                               "weights": weights}, "bincount", "GB/s")
+        self.mode, self.num_bins = mode, num_bins
+        reach = min(num_bins, 256) if dtype == "u8" else num_bins  # the bins the samples are spread over
+        u = ops.rand_uniform_(torch.empty(n, device=dev), 13000 + ctx.rank, 0.0, 1.0)
+        if dist == "zipf":
+            b = torch.exp(u * float(torch.log(torch.tensor(float(reach) + 1.0)))).long() - 1
+        else:
+            b = (u * reach).long()
+        b.clamp_(0, reach - 1)
+        del u
+        if dist == "equal":
+            b.fill_(reach // 2)
+        elif dist == "sorted":
+            b = torch.sort(b).values
+        if dtype == "f32":
+            self.x = ((b.float() + 0.5) / float(num_bins))
+        else:
+            self.x = b.to(torch.uint8 if dtype == "u8" else torch.int32)
+        del b
+        self.edges = torch.linspace(0.0, 1.0, num_bins + 1, device=dev) if mode == "edges" else None
+        self.w = None
+        if weights != "none":
+            w = ops.rand_uniform_(torch.empty(n, device=dev), 14000 + ctx.rank, 0.0, 1.0)
+            self.w = w if weights == "f32" else (w * 1000.0).int()
+        self.out = None
+
+    def step(self):
+        if self.mode == "bincount":
+            self.out = ops.bincount(self.x, self.num_bins, self.w)
+        elif self.mode == "histc":
+            self.out = ops.histc(self.x, self.num_bins, 0.0, 1.0)
+        else:
+            self.out = ops.histogram(self.x, self.edges)
+
+    def torch_step(self):
+        """The torch call this replaces: torch.bincount (int64 counts, float atomics with float weights), torch.histc
+        (float counts), or bucketize + bincount for explicit edges (torch.histogram has no GPU kernel)."""
+        if self.mode == "bincount":
+            return torch.bincount(self.x, weights=self.w, minlength=self.num_bins)
+        if self.mode == "histc":
+            return torch.histc(self.x, self.num_bins, 0.0, 1.0)
+        return torch.bincount((torch.bucketize(self.x, self.edges, right=True) - 1).clamp_(0, self.num_bins - 1),
+                              minlength=self.num_bins)
+
+    def work_per_step(self):
+        return float(self.x.numel() * (self.x.element_size() + (4 if self.w is not None else 0)))  # bytes read once
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gsamples_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        return rep
+
+    def oracle_bins(self) -> torch.Tensor:
+        """int64 bin of every sample that falls in a bin, by the ops' definitions written with separate torch ops."""
+        x, nb = self.x.reshape(-1), self.num_bins
+        if self.mode == "bincount":
+            v = x.long()
+            return v[(v >= 0) & (v < nb)]
+        if self.mode == "histc":
+            lo, hi = torch.tensor(0.0, device=x.device), torch.tensor(1.0, device=x.device)
+            scale = torch.tensor(float(nb), dtype=torch.float32, device=x.device) / (hi - lo)
+            v = x[(x >= lo) & (x <= hi)]
+            return ((v - lo) * scale).to(torch.int64).clamp(max=nb - 1)
+        v = x[(x >= self.edges[0]) & (x <= self.edges[-1])]
+        return (torch.bucketize(v, self.edges, right=True) - 1).clamp(0, nb - 1)
+
+    def check(self, reduce: bool = True):
+        """The counts of the timed step against torch.bincount of the oracle bins, exactly (int32 weights: int64 sums
+        wrapped to int32, exactly; float32 weights: every bin within (m - 1) * 2^-24 * sum|w| of the fp64 sum, m the
+        samples of the bin, the bound of any summation order). Local only."""
+        nb = self.num_bins
+        b = self.oracle_bins()
+        if self.w is None:
+            ok = self.out.dtype == torch.int32 and torch.equal(self.out, torch.bincount(b, minlength=nb).int())
+        else:
+            v = self.x.reshape(-1).long()
+            w = self.w.reshape(-1)[(v >= 0) & (v < nb)]
+            if w.dtype == torch.int32:
+                s = torch.zeros(nb, dtype=torch.int64, device=w.device).index_add_(0, b, w.long())
+                ok = self.out.dtype == torch.int32 and torch.equal(self.out.long(), ((s + (1 << 31)) % (1 << 32)) - (1 << 31))
+            else:
+                z = torch.zeros(nb, dtype=torch.float64, device=w.device)
+                s, sa = z.clone().index_add_(0, b, w.double()), z.clone().index_add_(0, b, w.double().abs())
+                m = torch.bincount(b, minlength=nb).double()
+                bound = (m - 1).clamp_min(0) * 2.0 ** -24 * sa
+                ok = self.out.dtype == torch.float32 and bool(((self.out.double() - s).abs() <= bound).all())
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"samples_counted": int(b.numel()), "elements_checked": self.x.numel(), "exact_vs_torch": ok,
+                "check_passed": ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
-             "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey}
+             "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

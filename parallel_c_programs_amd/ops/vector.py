@@ -666,3 +666,193 @@ def run_positions(keys: torch.Tensor) -> torch.Tensor:
     head = _key_heads(keys)
     start = torch.cummax(torch.where(head, torch.arange(n), 0), 0).values if n else torch.arange(0)
     return (torch.arange(n) - start).int().reshape(keys.shape)
+
+
+# ---------------------------------------------------------------- histograms (bincount / histc / explicit edges)
+# int32 counts of x.flatten() per bin: bincount (the value of an int32 / uint8 sample is its bin), histc (equal-width
+# float32 bins of [lo, hi]) and histogram (float32 bins between ascending edges). The generalisation of program 4's
+# 256-bin image histogram; on the GPU one persistent kernel per form (csrc/kernels/bincount.hip): counters in LDS up to
+# HIST_LDS_BINS bins (replicated and bank-rotated while they fit several times), in LDS with the bins cut into ranges
+# and the input read once per range up to HIST_RANGED_BINS, straight integer atomics above, no block waits for
+# another. Common rules:
+#  * Counts are int32 (as unique / run_length_encode give), exact, and the same on every call. Fewer than 2^31 samples.
+#  * A sample that falls in no bin is IGNORED (never an error): a negative or too large int, a float outside the range,
+#    NaN, +-inf.
+#  * out (optional): 1-D, exactly num_bins entries, int32 (float32 with float32 weights), on x's device; overwritten.
+#    accumulate=True adds into out instead (a histogram over chunks). x is never written. An empty x gives zeros, or
+#    leaves an accumulated out as it is.
+#  * Nothing synchronises, except bincount(num_bins=None), which reads the largest sample (one sync).
+#  * Measured on one MI355X at 2^28 samples (profiles/r12_bincount/README.md): int32 bincount 0.18 ms up to 24576 bins
+#    for uniform, all-in-one-bin, sorted and zipf samples alike (1.06-1.10x a copy of the same bytes; torch.bincount
+#    1.0-11.8 ms; unique with counts 5.8-8.2 ms), 0.34 ms at 24577 bins, 7.6 ms at 1572864, 9.9 ms above (torch 11.9);
+#    uint8 0.093 ms; histc 0.27 ms at 256 bins (torch.histc 1.34); histogram 1.35 ms at 64 bins, 3.1 at 8192. The
+#    weakest case is a zipf-like skew above HIST_RANGED_BINS: 216 ms (torch 237). float32 weights are SLOWER than
+#    torch.bincount: 16.8 against 1.95 ms at 256 bins (the sort).
+HIST_LDS_BINS = 24576     # csrc/kernels/bincount.hip kLdsBins: the counters of all bins fit one block's LDS up to here
+HIST_RANGED_BINS = 64 * HIST_LDS_BINS  # kMaxRanges * kLdsBins: LDS counting over bin ranges up to here, global atomics above
+HIST_MAX_EDGE_BINS = 8192  # histogram(): the edges live in LDS beside the counters
+
+
+def _check_hist_common(x: torch.Tensor, num_bins: int, out, accumulate: bool, out_dtype: torch.dtype, name: str) -> None:
+    if x.numel() >= 1 << 31:
+        raise ValueError(f"{name}: x has {x.numel()} elements; counts are int32 (fewer than 2^31)")
+    if accumulate and out is None:
+        raise ValueError(f"{name}: accumulate=True needs out")
+    if out is None:
+        return
+    if out.dtype != out_dtype:
+        raise TypeError(f"{name}: out must be {out_dtype}, got {out.dtype}")
+    if out.device != x.device:
+        raise ValueError(f"{name}: out is on {out.device}, x on {x.device}")
+    if out.dim() != 1 or out.numel() != num_bins:
+        raise ValueError(f"{name}: out must be 1-D with exactly {num_bins} entries, got shape {tuple(out.shape)}")
+
+
+def _wrap_i32(s: torch.Tensor) -> torch.Tensor:
+    return (((s + (1 << 31)) % (1 << 32)) - (1 << 31)).int()
+
+
+def _host_counts(bins_of_kept: torch.Tensor, num_bins: int, amounts: torch.Tensor | None, out, accumulate: bool):
+    """The CPU paths' result: int64 sums per bin over the kept samples (1 each, or amounts), wrapped to int32."""
+    add = torch.ones_like(bins_of_kept) if amounts is None else amounts.long()
+    c = _wrap_i32(torch.zeros(num_bins, dtype=torch.int64).index_add_(0, bins_of_kept, add))
+    if out is None:
+        return c
+    if accumulate:
+        c = _wrap_i32(out.long() + c.long())
+    out.copy_(c)
+    return out
+
+
+def _bincount_f32_weights(keys: torch.Tensor, weights: torch.Tensor, num_bins: int, out, accumulate: bool):
+    """sum of float32 weights per bin without float atomics: stable sort by key, fixed-order sum per run, scatter of
+    the run sums. Runs whose key is no bin, and the unwritten tail past num_runs, go to a discarded extra slot, so
+    nothing has to be read back."""
+    n = keys.numel()
+    if n == 0:
+        return out if out is not None and accumulate else (
+            out.zero_() if out is not None else torch.zeros(num_bins, dtype=torch.float32, device=keys.device))
+    ks, vs = sort_by_key(keys, weights.reshape(-1))
+    rk, ra, num = reduce_by_key(ks, vs, "sum")
+    live = (torch.arange(n, device=keys.device) < num) & (rk >= 0) & (rk < num_bins)
+    slot = torch.where(live, rk.long(), num_bins)
+    dense = torch.zeros(num_bins + 1, dtype=torch.float32, device=keys.device).scatter_(0, slot, ra)[:num_bins]
+    if out is None:
+        return dense
+    if accumulate:
+        out.add_(dense)
+    else:
+        out.copy_(dense)
+    return out
+
+
+def bincount(x: torch.Tensor, num_bins: int | None = None, weights: torch.Tensor | None = None,
+             out: torch.Tensor | None = None, accumulate: bool = False) -> torch.Tensor:
+    """out[b] = how many samples of x.flatten() (int32 or uint8) equal b, for b in [0, num_bins), as int32; samples
+    below 0 or at or above num_bins are ignored. num_bins=None sizes the result like torch.bincount, max + 1 (0 bins
+    for an empty x): ONE host sync, and ValueError on a negative sample. weights (same numel and device): int32 weights
+    are summed per bin in the same kernel, int32 result, sums wrap mod 2^32 and are exact. float32 weights give a
+    float32 result with the same bits on every call (no float atomics): that route COSTS A SORT (sort_by_key, then
+    reduce_by_key's fixed-order sums, then a scatter; at most SORT_MAX_N samples) and is far slower than the integer
+    forms. out / accumulate: see the rules above. Does not synchronise when num_bins is given."""
+    if x.dtype not in (torch.int32, torch.uint8):
+        raise TypeError(f"bincount: x must be int32 or uint8, got {x.dtype}")
+    if weights is not None:
+        if weights.dtype not in (torch.int32, torch.float32):
+            raise TypeError(f"bincount: weights must be int32 or float32, got {weights.dtype}")
+        if weights.numel() != x.numel():
+            raise ValueError(f"bincount: {weights.numel()} weights for {x.numel()} samples")
+        if weights.device != x.device:
+            raise ValueError(f"bincount: weights are on {weights.device}, x on {x.device}")
+    if num_bins is None:
+        if x.numel() == 0:
+            num_bins = 0
+        else:
+            lo, hi = torch.stack(torch.aminmax(x)).tolist()  # the one host sync
+            if lo < 0:
+                raise ValueError(f"bincount: num_bins=None needs non-negative samples, the smallest is {lo}")
+            num_bins = int(hi) + 1
+    elif isinstance(num_bins, bool) or not isinstance(num_bins, int):
+        raise TypeError(f"bincount: num_bins must be an int or None, got {type(num_bins).__name__}")
+    elif not 1 <= num_bins < 1 << 31:
+        raise ValueError(f"bincount: num_bins must be in 1..2^31 - 1, got {num_bins}")
+    fw = weights is not None and weights.dtype == torch.float32
+    _check_hist_common(x, num_bins, out, accumulate, torch.float32 if fw else torch.int32, "bincount")
+    if num_bins == 0:
+        return out if out is not None else torch.zeros(0, dtype=torch.float32 if fw else torch.int32, device=x.device)
+    if fw:
+        return _bincount_f32_weights(x.reshape(-1).int(), weights, num_bins, out, bool(accumulate))
+    if x.is_cuda:
+        return ops().bincount(x, num_bins, weights, out, bool(accumulate))
+    v = x.reshape(-1).long()
+    keep = (v >= 0) & (v < num_bins)
+    return _host_counts(v[keep], num_bins, None if weights is None else weights.reshape(-1)[keep], out, bool(accumulate))
+
+
+def _histc_scale(bins: int, lo: float, hi: float):
+    """(lo, hi, scale) as the float32 values the definition uses; ValueError for a range that is empty, reversed, not
+    finite, or no longer a finite positive width in float32."""
+    if isinstance(bins, bool) or not isinstance(bins, int):
+        raise TypeError(f"histc: bins must be an int, got {type(bins).__name__}")
+    if not 1 <= bins < 1 << 31:
+        raise ValueError(f"histc: bins must be in 1..2^31 - 1, got {bins}")
+    lo32, hi32 = torch.tensor(float(lo), dtype=torch.float32), torch.tensor(float(hi), dtype=torch.float32)
+    width = hi32 - lo32
+    if not (torch.isfinite(lo32) and torch.isfinite(hi32) and torch.isfinite(width) and lo32 < hi32):
+        raise ValueError(f"histc: lo < hi, both finite in float32 with a finite width, got lo={lo}, hi={hi}")
+    scale = torch.tensor(float(bins), dtype=torch.float32) / width
+    if not torch.isfinite(scale):
+        raise ValueError(f"histc: {bins} bins over [{lo}, {hi}] have no finite float32 scale")
+    return lo32, hi32, scale
+
+
+def histc(x: torch.Tensor, bins: int, lo: float, hi: float, out: torch.Tensor | None = None,
+          accumulate: bool = False) -> torch.Tensor:
+    """int32 counts of the float32 samples of x.flatten() in `bins` equal-width bins of [lo, hi] (bins >= 1, lo < hi,
+    both finite; else ValueError). The bin is DEFINED by this float32 sequence, every step rounded on its own (no FMA):
+        scale = float32(bins) / (float32(hi) - float32(lo))        once, on the host
+        bin   = min(int((v - lo) * scale), bins - 1)                counted only when lo <= v <= hi
+    so v == hi falls in the last bin and NaN, +-inf and samples outside the range are ignored (the range is compared
+    in float before anything is converted). The definition is ours: torch.histc returns floats, and its CPU and GPU
+    builds place samples that lie within rounding distance of a bin border differently (they compute the bin by other,
+    mutually different formulas). All of them agree with this one wherever the arithmetic is exact, e.g. a
+    power-of-two range with samples on a dyadic grid, and everywhere away from the borders. out / accumulate: see the
+    rules above. Does not synchronise."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"histc: x must be float32, got {x.dtype}")
+    lo32, hi32, scale = _histc_scale(bins, lo, hi)
+    _check_hist_common(x, bins, out, accumulate, torch.int32, "histc")
+    if x.is_cuda:
+        return ops().hist_even(x, bins, lo32.item(), hi32.item(), scale.item(), out, bool(accumulate))
+    v = x.reshape(-1)
+    v = v[(v >= lo32) & (v <= hi32)]
+    b = ((v - lo32) * scale).to(torch.int64).clamp(max=bins - 1)
+    return _host_counts(b, bins, None, out, bool(accumulate))
+
+
+def histogram(x: torch.Tensor, edges: torch.Tensor, out: torch.Tensor | None = None,
+              accumulate: bool = False) -> torch.Tensor:
+    """int32 counts of the float32 samples of x.flatten() in the B bins between the B + 1 ascending float32 values of
+    the 1-D tensor edges (on x's device, 1 <= B <= HIST_MAX_EDGE_BINS = 8192): bin i holds edges[i] <= v < edges[i+1],
+    the last bin also v == edges[B] (the numpy / torch.histogram rule; repeated edges give empty bins). NaN and samples
+    outside [edges[0], edges[B]] are ignored. Ascending order is the caller's duty: unsorted edges give unspecified
+    counts, but every index of the search is clamped, so nothing outside the tensors is touched. out / accumulate: see
+    the rules above. Does not synchronise."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"histogram: x must be float32, got {x.dtype}")
+    if edges.dtype != torch.float32:
+        raise TypeError(f"histogram: edges must be float32, got {edges.dtype}")
+    if edges.device != x.device:
+        raise ValueError(f"histogram: edges are on {edges.device}, x on {x.device}")
+    if edges.dim() != 1 or edges.numel() < 2:
+        raise ValueError(f"histogram: edges must be 1-D with at least 2 values, got shape {tuple(edges.shape)}")
+    nb = edges.numel() - 1
+    if nb > HIST_MAX_EDGE_BINS:
+        raise ValueError(f"histogram: {nb} bins; the limit is {HIST_MAX_EDGE_BINS} (the edges are kept in LDS)")
+    _check_hist_common(x, nb, out, accumulate, torch.int32, "histogram")
+    if x.is_cuda:
+        return ops().hist_range(x, edges, out, bool(accumulate))
+    v = x.reshape(-1)
+    v = v[(v >= edges[0]) & (v <= edges[nb])]
+    b = (torch.searchsorted(edges.contiguous(), v, right=True) - 1).clamp(0, nb - 1)
+    return _host_counts(b, nb, None, out, bool(accumulate))
