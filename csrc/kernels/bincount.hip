@@ -39,6 +39,7 @@
 #include "pcmx_hip.h"
 
 namespace {
+using pcmx::device_cus;
 using pcmx::kWave;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -310,15 +311,6 @@ __global__ __launch_bounds__(kThreads) void bincount_kernel(const Args a) {
             if (sum != 0u) atomicAdd(a.out + bin0 + b, sum);
         }
     }
-}
-
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
 }
 
 // out_bins: entries of out (all zeroed unless accumulate); a.bins: the bins a sample can reach

@@ -22,32 +22,25 @@
 //    gives up marks its result invalid in the workspace (ws->timeout) AND in the caller's sticky error word
 //    (err_flag, system-scope atomic OR: it may live in host-mapped pinned memory), which pcmx_scan_check /
 //    the torch op turn into an error instead of a silently wrong prefix.
+#include "lookback.h"
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
 
 namespace {
+using pcmx::device_cus;
 using pcmx::f32x4;
+using pcmx::kFlagAgg;
+using pcmx::kFlagIncl;
+using pcmx::kSpinLimit;
 using pcmx::kWave;
-constexpr unsigned kFlagAgg = 1u, kFlagIncl = 2u;
+using pcmx::report_timeout;
 #ifdef PCMX_FAULT_INJECT
-// test-only build (libpcmx_faultinj.so): the look-back of tile 1 never sees its predecessor and gives up fast
-constexpr unsigned kSpinLimit = 64u;
-constexpr long long kFaultTile = 1;
-#else
-constexpr unsigned kSpinLimit = 1u << 26;
+using pcmx::kFaultTile;
 #endif
 constexpr int kTileElems = 32768;  // 128 KiB of f32 for every variant
 
-struct ScanWs {
-    unsigned ticket;
-    unsigned timeout;
-    unsigned pad[2];
-    // followed by unsigned long long status[num_tiles]
-};
-
-__device__ __forceinline__ unsigned long long pack(unsigned flag, float v) {
-    return ((unsigned long long)flag << 32) | (unsigned long long)__float_as_uint(v);
-}
+typedef pcmx::LookbackHeader ScanWs;  // followed by unsigned long long status[num_tiles]
+typedef pcmx::GranuleF32 Granule;
 
 // W waves x R f32x4 rows per lane; wave w owns the contiguous R*256 elements starting at w*R*256.
 template <int R, int W>
@@ -107,14 +100,6 @@ __device__ __forceinline__ void store_row(float* out, long long n, long long e, 
     }
 }
 
-// A look-back that ran out of spins: marks the result invalid in the workspace and in the caller's sticky word.
-__device__ __forceinline__ void report_timeout(ScanWs* ws, unsigned* err_flag) {
-    if (pcmx::lane_id() == 0) {
-        atomicExch(&ws->timeout, 1u);
-        if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
 // Scans tile `tile` held in v, publishes it, issues the loads of `next` into vn, looks back, stores.
 template <int R, int W>
 __device__ __forceinline__ void finish_tile(const float* __restrict__ in, float* __restrict__ out, long long n, long long tile,
@@ -147,7 +132,7 @@ __device__ __forceinline__ void finish_tile(const float* __restrict__ in, float*
         agg += t;
     }
     if (threadIdx.x == 0)
-        __hip_atomic_store(&status[tile], pack(tile == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
+        __hip_atomic_store(&status[tile], Granule::pack(tile == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     // ---- the next tile's loads go out now and overlap the look-back below
     if (next < ntiles) load_tile<R, W>(in, n, next, vn);
@@ -160,44 +145,7 @@ __device__ __forceinline__ void finish_tile(const float* __restrict__ in, float*
 
     // ---- wave 0: decoupled look-back over the predecessors' {flag, value} granules
     if (wave == 0) {
-        float prefix = 0.f;
-        if (tile != 0) {
-            long long look = tile - 1;  // newest predecessor still to account for
-            unsigned spins = 0;
-            while (true) {
-                const long long idx = look - lane;
-                unsigned long long sv =
-                    idx >= 0 ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : pack(kFlagIncl, 0.f);
-#ifdef PCMX_FAULT_INJECT
-                if (tile == kFaultTile) sv = 0ull;  // fault injection: this tile never sees its predecessors
-#endif
-                const unsigned flag = (unsigned)(sv >> 32);
-                const float val = __uint_as_float((unsigned)sv);
-                const unsigned long long m_incl = __ballot(flag == kFlagIncl);
-                const unsigned long long m_zero = __ballot(flag == 0u);
-                if (m_incl != 0ull) {
-                    const int first = __builtin_ctzll(m_incl);
-                    const unsigned long long need = (first == 63) ? ~0ull : ((1ull << (first + 1)) - 1ull);
-                    if ((m_zero & need) == 0ull) {
-                        prefix += pcmx::wave_reduce<float, 0>(lane <= first ? val : 0.f);
-                        break;
-                    }
-                } else if (m_zero == 0ull) {
-                    prefix += pcmx::wave_reduce<float, 0>(val);
-                    look -= kWave;
-                    continue;
-                }
-                if (++spins > kSpinLimit) {  // bounded spin: report (workspace + sticky caller word) and fall through
-                    report_timeout(ws, err_flag);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (lane == 0)
-                __hip_atomic_store(&status[tile], pack(kFlagIncl, prefix + agg), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
+        const float prefix = pcmx::lookback_publish<Granule>(ws, status, tile, agg, err_flag);
         if (lane == 0) *s_prefix = init + prefix;
     }
     if (threadIdx.x == 0) *s_next = ticket;
@@ -266,7 +214,7 @@ __device__ __forceinline__ void parked_poll(long long tile, long long look, Scan
     for (int k = 0; k < kParkWindows; ++k) {
         const long long idx = look - lane - (long long)k * kWave;
         sv[k] = idx >= 0 ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                         : pack(kFlagIncl, 0.f);
+                         : Granule::pack(kFlagIncl, 0.f);
 #ifdef PCMX_FAULT_INJECT
         if (tile == kFaultTile) sv[k] = 0ull;
 #endif
@@ -288,8 +236,8 @@ __device__ __forceinline__ float parked_lookback(long long tile, ScanWs* ws, uns
 #pragma unroll
         for (int k = 0; k < kParkWindows; ++k) {
             if (done || stall) break;  // wave-uniform
-            const unsigned flag = (unsigned)(sv[k] >> 32);
-            const float val = __uint_as_float((unsigned)sv[k]);
+            const unsigned flag = Granule::flag(sv[k]);
+            const float val = Granule::value(sv[k]);
             const unsigned long long m_incl = __ballot(flag == kFlagIncl);
             const unsigned long long m_zero = __ballot(flag == 0u);
             if (m_incl != 0ull) {
@@ -311,7 +259,7 @@ __device__ __forceinline__ float parked_lookback(long long tile, ScanWs* ws, uns
         if (done) break;
         if (stall) {
             if (++spins > kSpinLimit) {  // bounded spin, reported as in the persistent schedule
-                report_timeout(ws, err_flag);
+                if (lane == 0) report_timeout(ws, err_flag);
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -332,7 +280,7 @@ __device__ __forceinline__ void parked_flush(float* __restrict__ out, long long 
         const float prefix = prev == 0 ? 0.f : parked_lookback(prev, ws, err_flag, sv, polled);
         if (lane == 0) {
             if (prev != 0)
-                __hip_atomic_store(&status[prev], pack(kFlagIncl, prefix + agg_prev), __ATOMIC_RELAXED,
+                __hip_atomic_store(&status[prev], Granule::pack(kFlagIncl, prefix + agg_prev), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
             *s_prefix = init + prefix;
         }
@@ -389,7 +337,7 @@ __device__ __forceinline__ float parked_step(const float* __restrict__ in, float
         agg += t;
     }
     if (threadIdx.x == 0)
-        __hip_atomic_store(&status[cur], pack(cur == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
+        __hip_atomic_store(&status[cur], Granule::pack(cur == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     if (next < ntiles) load_tile<R, W>(in, n, next, vn);
     const unsigned ticket = threadIdx.x == 0 ? atomicAdd(&ws->ticket, 1u) : 0u;
@@ -439,15 +387,6 @@ __global__ __launch_bounds__(W * kWave) void scan_parked_kernel(const float* __r
 }
 
 inline long long num_tiles(long long n) { return (n + kTileElems - 1) / kTileElems; }
-
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
 }  // namespace
 
 extern "C" long long pcmx_scan_workspace_bytes(long long n) { return (long long)sizeof(ScanWs) + num_tiles(n) * 8; }

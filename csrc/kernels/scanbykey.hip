@@ -3,7 +3,7 @@
 // flags marks. The sibling of segreduce.hip, which writes one aggregate per run; this one writes every element. No
 // counterpart in the reference programs.
 //
-// Shared with segreduce.hip (copied, not included: that file's generated code stays as it is): the persistent schedule
+// Shared with segreduce.hip (the tile shape through tile_bits.h; the rest copied, the bodies differ): the persistent schedule
 // (one 512-thread block per CU, 32768-element tiles from an atomic ticket), the key and value loads, the head bits
 // from the neighbouring key bits (the lane's own row, DPP wave_shr:1, v_readlane of the previous row's lane 63, one
 // extra load per wave; the keys are read once) and the in-tile segmented scan in a fixed order (a lane's 4 elements,
@@ -37,15 +37,17 @@
 
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "tile_bits.h"
 
 namespace {
+using pcmx::device_cus;
+using pcmx::from_lane_below;
 using pcmx::kWave;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kRows = 16, kWaves = 8;                 // 16 rows of 4 elements per lane, 8 waves
-constexpr int kWaveItems = kRows * 4 * kWave;         // 4096 contiguous elements per wave
-constexpr int kTileElems = kWaves * kWaveItems;       // 32768
-constexpr unsigned kHasHead = 1u << 31;               // tile_meta: the tile holds a run head; low bits: lead length
+using pcmx::misaligned;
+using pcmx::pad4;
+using pcmx::u32x4;
+using namespace pcmx::tile_bits;         // the tile shape
+constexpr unsigned kHasHead = 1u << 31;  // tile_meta: the tile holds a run head; low bits: lead length
 enum { kSrcOne = 0, kSrcI32 = 1, kSrcF32 = 2 };
 
 struct SbkWs {
@@ -54,11 +56,6 @@ struct SbkWs {
     // followed by unsigned tile_meta[tiles4], 4-byte tile_closing[tiles4], 4-byte tile_carry[tiles4]
     // (tiles4 = tiles padded to a multiple of 4); every entry below `tiles` is written before it is read
 };
-
-// lane l gets lane l-1's value (DPP wave_shr:1); lane 0 gets 0
-__device__ __forceinline__ unsigned from_lane_below(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
-}
 
 template <class T, int OP>
 __device__ __forceinline__ T identity() {
@@ -96,8 +93,6 @@ struct Vec4 {
     typedef T type __attribute__((ext_vector_type(4)));
 };
 
-__host__ __device__ inline long long pad4(long long t) { return (t + 3) & ~3LL; }
-
 struct SideArrays {
     unsigned* tile_meta;  // lead length | kHasHead
     void* tile_closing;   // aggregate of the elements after the tile's last head (the whole tile when it has none)
@@ -112,7 +107,8 @@ __host__ __device__ inline SideArrays side_arrays(void* ws, long long tiles) {
     return s;
 }
 
-// Bit 4r+j of the result: element j of row r of this lane lies below n (all ones for a full tile).
+// Bit 4r+j of the result: element j of row r of this lane lies below n (all ones for a full tile). (The same bound
+// as tile_bits.h's drop_past_n, built as a mask: switching to that form changes this kernel's generated code.)
 __device__ __forceinline__ unsigned long long valid_bits(long long n, long long tile) {
     if ((tile + 1) * kTileElems <= n) return ~0ull;  // block-uniform
     const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
@@ -455,17 +451,6 @@ __global__ __launch_bounds__(kLeadThreads) void scanbykey_lead_kernel(T* __restr
 
 inline long long num_tiles(long long n) { return (n + kTileElems - 1) / kTileElems; }
 inline size_t ws_bytes(long long tiles) { return sizeof(SbkWs) + (size_t)pad4(tiles) * 12; }
-
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
-
-inline bool misaligned(const void* p, unsigned mask = 15u) { return (((uintptr_t)p) & mask) != 0; }
 
 template <int FLAGS, int SRC, class T, int OP>
 int launch_op(const void* keys_or_heads, const T* vals, T* out, long long n, int exclusive, void* workspace, hipStream_t s) {

@@ -2,11 +2,10 @@
 // 32-bit keys and reduces a value stream (the constant 1, int32 or float32; sum, min or max) per run. No counterpart
 // in the reference programs; the by-key member of the scan / select / sort family.
 //
-// Shared with select.hip (and through it scan.hip): the persistent schedule (one 512-thread block per CU, 32768-key
-// tiles from the atomic ticket), the look-back itself
-// (8-byte {flag, count} granules, one agent-scope relaxed store, relaxed polls, bounded spins, ws->timeout plus the
-// caller's sticky error word), hipMemsetAsync of the workspace per launch, the header layout (pcmx_scan_check reads
-// this workspace), and the ballot / v_mbcnt lane offsets. The keep bit is the run head, key[i] != key[i-1] compared
+// Shared with select.hip: the persistent schedule (one 512-thread block per CU, 32768-key tiles from the atomic
+// ticket), the look-back (lookback.h: 8-byte {flag, count} granules, bounded spins, ws->timeout plus the caller's
+// sticky error word, the header that pcmx_scan_check reads), hipMemsetAsync of the workspace per launch, and the
+// ballot / v_mbcnt lane offsets (tile_bits.h). The keep bit is the run head, key[i] != key[i-1] compared
 // as bit patterns; the look-back carries only the integer count of heads, so every output position is exact.
 // What differs:
 //  * The neighbour key comes from the lane's own row (4 keys), the lane below (DPP wave_shr:1), the previous row's
@@ -36,42 +35,29 @@
 
 #include <type_traits>
 
+#include "lookback.h"
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "tile_bits.h"
 
 namespace {
+using pcmx::device_cus;
+using pcmx::from_lane_below;
+using pcmx::kFlagAgg;
+using pcmx::kFlagIncl;
 using pcmx::kWave;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kFlagAgg = 1u, kFlagIncl = 2u;
-constexpr unsigned kSpinLimit = 1u << 26;
-constexpr int kRows = 16, kWaves = 8;                 // 16 rows of 4 elements per lane, 8 waves
-constexpr int kWaveItems = kRows * 4 * kWave;         // 4096 contiguous elements per wave
-constexpr int kTileElems = kWaves * kWaveItems;       // 32768 (128 KiB of keys)
-constexpr unsigned kFirstIsHead = 1u << 31;           // tile_meta: the tile's first element starts a run
+using pcmx::misaligned;
+using pcmx::pad2;
+using pcmx::pad4;
+using pcmx::u32x4;
+using namespace pcmx::tile_bits;             // the tile shape (128 KiB of keys) and the per-element bit helpers
+constexpr unsigned kFirstIsHead = 1u << 31;  // tile_meta: the tile's first element starts a run
 enum { kSrcOne = 0, kSrcI32 = 1, kSrcF32 = 2 };
 
-// Same layout as the scan's workspace header, so pcmx_scan_check reads a segreduce workspace too.
-struct SegWs {
-    unsigned ticket;
-    unsigned timeout;
-    unsigned pad[2];
-    // followed by unsigned long long status[tiles, padded to even], unsigned tile_p[tiles4], unsigned
-    // tile_meta[tiles4], 4-byte tile_lead[tiles4] (tiles4 = tiles padded to a multiple of 4)
-};
-
-__device__ __forceinline__ unsigned long long pack(unsigned flag, unsigned v) {
-    return ((unsigned long long)flag << 32) | (unsigned long long)v;
-}
-
-__device__ __forceinline__ unsigned lanes_below(unsigned long long ballot, unsigned acc) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, acc));
-}
-
-// lane l gets lane l-1's value (DPP wave_shr:1); lane 0 gets 0
-__device__ __forceinline__ unsigned from_lane_below(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
-}
+// followed by unsigned long long status[tiles, padded to even], unsigned tile_p[tiles4], unsigned tile_meta[tiles4],
+// 4-byte tile_lead[tiles4] (tiles4 = tiles padded to a multiple of 4)
+typedef pcmx::LookbackHeader SegWs;
+typedef pcmx::GranuleU32 Granule;  // the tile's count of run heads
 
 template <class T, int OP>
 __device__ __forceinline__ T identity() {
@@ -205,24 +191,7 @@ __device__ __forceinline__ unsigned long long head_bits(const TileKeys& t, long 
         bits |= (unsigned long long)h << (4 * r);
         before = (unsigned)__builtin_amdgcn_readlane((int)k.w, 63);
     }
-    if ((tile + 1) * kTileElems > n) {  // block-uniform: the last tile drops every element at or past n
-        const int rem = (int)(n - tile * kTileElems);
-        const int base = wave * kWaveItems + lane * 4;
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const int left = rem - (base + r * 256);
-            const unsigned ok = left >= 4 ? 0xfu : (left <= 0 ? 0u : ((1u << left) - 1u));
-            bits &= ~((unsigned long long)(0xfu & ~ok) << (4 * r));
-        }
-    }
-    return bits;
-}
-
-__device__ __forceinline__ void report_timeout(SegWs* ws, unsigned* err_flag) {
-    if (pcmx::lane_id() == 0) {
-        atomicExch(&ws->timeout, 1u);
-        if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    return drop_past_n(bits, n, tile);
 }
 
 // The side arrays behind the granules.
@@ -231,9 +200,6 @@ struct SideArrays {
     unsigned* tile_meta;  // heads in the tile | kFirstIsHead
     void* tile_lead;      // aggregate of the elements before the tile's first head (the whole tile when it has none)
 };
-
-__host__ __device__ inline long long pad2(long long t) { return (t + 1) & ~1LL; }
-__host__ __device__ inline long long pad4(long long t) { return (t + 3) & ~3LL; }
 
 __host__ __device__ inline SideArrays side_arrays(void* ws, long long tiles) {
     unsigned long long* status = reinterpret_cast<unsigned long long*>(static_cast<SegWs*>(ws) + 1);
@@ -270,70 +236,25 @@ __device__ __forceinline__ void process_tile(const unsigned* __restrict__ keys, 
     load_vals<SRC, T, OP>(vals, n, tile, v);
     // ---- head bits, then per row the integer wave prefix of the heads (input order: row, lane, element)
     const unsigned long long bits = head_bits(t, n, tile);
-    unsigned carry = 0u;  // wave-uniform: heads of the rows before r
+    unsigned carry;  // wave-uniform: the wave's heads
     unsigned lane_off[kRows];
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const unsigned k = (unsigned)(bits >> (4 * r)) & 0xfu;
-        const unsigned long long b0 = __ballot(k & 1u), b1 = __ballot(k & 2u), b2 = __ballot(k & 4u), b3 = __ballot(k & 8u);
-        lane_off[r] = lanes_below(b3, lanes_below(b2, lanes_below(b1, lanes_below(b0, carry))));
-        carry += (unsigned)(__popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3));
-        asm volatile("" : "+v"(lane_off[r]));  // materialised here, as in select.hip
-    }
+    rank_rows(bits, lane_off, carry);
     if (lane == 0) s_wave_tot[wave] = carry;
     __syncthreads();
-    unsigned agg = 0u, wexcl = 0u;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const unsigned c = s_wave_tot[w];
-        wexcl += w < wave ? c : 0u;
-        agg += c;
-    }
+    unsigned agg, wexcl;
+    fold_wave_totals(s_wave_tot, agg, wexcl);
     const bool tile_starts_run = ((unsigned)bits & 1u) != 0u;  // meaningful in thread 0: it holds the tile's element 0
     if (threadIdx.x == 0) {
-        __hip_atomic_store(&status[tile], pack(tile == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
+        __hip_atomic_store(&status[tile], Granule::pack(tile == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
         side.tile_meta[tile] = agg | (tile_starts_run ? kFirstIsHead : 0u);
         *s_next = atomicAdd(&ws->ticket, 1u);  // the ticket of this block's next tile
     }
 
-    // ---- wave 0: decoupled look-back over the predecessors' {flag, head count} granules (select.hip's)
+    // ---- wave 0: decoupled look-back over the predecessors' {flag, head count} granules
     if (wave == 0) {
-        unsigned prefix = 0u;
-        if (tile != 0) {
-            long long look = tile - 1;
-            unsigned spins = 0;
-            while (true) {
-                const long long idx = look - lane;
-                const unsigned long long sv =
-                    idx >= 0 ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : pack(kFlagIncl, 0u);
-                const unsigned flag = (unsigned)(sv >> 32);
-                const unsigned val = (unsigned)sv;
-                const unsigned long long m_incl = __ballot(flag == kFlagIncl);
-                const unsigned long long m_zero = __ballot(flag == 0u);
-                if (m_incl != 0ull) {
-                    const int first = __builtin_ctzll(m_incl);
-                    const unsigned long long need = (first == 63) ? ~0ull : ((1ull << (first + 1)) - 1ull);
-                    if ((m_zero & need) == 0ull) {
-                        prefix += pcmx::wave_reduce<unsigned, 0>(lane <= first ? val : 0u);
-                        break;
-                    }
-                } else if (m_zero == 0ull) {
-                    prefix += pcmx::wave_reduce<unsigned, 0>(val);
-                    look -= kWave;
-                    continue;
-                }
-                if (++spins > kSpinLimit) {  // bounded spin: report and fall through
-                    report_timeout(ws, err_flag);  // (a partial prefix is <= the true one: the stores stay inside out)
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (lane == 0)
-                __hip_atomic_store(&status[tile], pack(kFlagIncl, prefix + agg), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
+        // (after a give-up the partial prefix is <= the true one: the stores stay inside out)
+        const unsigned prefix = pcmx::lookback_publish<Granule>(ws, status, tile, agg, err_flag);
         if (lane == 0) {
             *s_prefix = prefix;
             side.tile_p[tile] = prefix;
@@ -511,17 +432,6 @@ __global__ __launch_bounds__(kFixWaves * kWave) void lead_fixup_kernel(T* __rest
 inline long long num_tiles(long long n) { return (n + kTileElems - 1) / kTileElems; }
 // header + one granule per tile + three 4-byte side arrays, each padded to 16 bytes (zeroed before every launch)
 inline size_t ws_bytes(long long tiles) { return sizeof(SegWs) + (size_t)pad2(tiles) * 8 + (size_t)pad4(tiles) * 12; }
-
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
-
-inline bool misaligned(const void* p) { return (((uintptr_t)p) & 15u) != 0; }
 
 template <int SRC, class T, int OP>
 int launch_op(const void* keys, const T* vals, long long n, void* run_keys, T* agg, int* starts, long long* num_runs_dev,

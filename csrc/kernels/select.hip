@@ -17,39 +17,26 @@
 //    positions, then streams [0, count) out coalesced. The direct scattered store from registers was built first and
 //    measured slower once half the elements are kept (0.48 -> 0.38 ms at keep 0.5, 0.63 -> 0.45 at 1.0 for 2^28 f32;
 //    equal below; profiles/r7_select/store_path_ab.txt).
-//  * Hand-off, workspace zeroing, bounded spins and the give-up report are the scan's: 8-byte {flag, count} granules,
+//  * Hand-off, workspace zeroing, bounded spins and the give-up report are lookback.h's: 8-byte {flag, count} granules,
 //    one agent-scope relaxed atomic store, agent-scope relaxed polls, hipMemsetAsync before every launch, and a
 //    look-back that gives up sets ws->timeout and ORs 1 into the caller's sticky error word.
+#include "lookback.h"
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "tile_bits.h"
 
 namespace {
+using pcmx::at;
+using pcmx::device_cus;
+using pcmx::kFlagAgg;
+using pcmx::kFlagIncl;
 using pcmx::kWave;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kFlagAgg = 1u, kFlagIncl = 2u;
-constexpr unsigned kSpinLimit = 1u << 26;
-constexpr int kRows = 16, kWaves = 8;                 // 16 rows of 4 elements per lane, 8 waves
-constexpr int kWaveItems = kRows * 4 * kWave;         // 4096 contiguous elements per wave
-constexpr int kTileElems = kWaves * kWaveItems;       // 32768 (128 KiB of payload)
+using pcmx::u32x4;
+using namespace pcmx::tile_bits;  // the tile shape (128 KiB of payload) and the per-element bit helpers
 enum { kModeMask = 0, kModeIndex = 1, kModePred = 2 };
 
-// Same layout as the scan's workspace header, so pcmx_scan_check reads a select workspace too.
-struct SelectWs {
-    unsigned ticket;
-    unsigned timeout;
-    unsigned pad[2];
-    // followed by unsigned long long status[num_tiles]
-};
-
-__device__ __forceinline__ unsigned long long pack(unsigned flag, unsigned v) {
-    return ((unsigned long long)flag << 32) | (unsigned long long)v;
-}
-
-// u32 wave prefix of one-bit items: how many lanes BELOW this one have their bit set in the ballot.
-__device__ __forceinline__ unsigned lanes_below(unsigned long long ballot, unsigned acc) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, acc));
-}
+typedef pcmx::LookbackHeader SelectWs;  // followed by unsigned long long status[num_tiles]
+typedef pcmx::GranuleU32 Granule;       // the tile's kept count
 
 // One tile's inputs in registers: payload rows (kModeMask, kModePred) and/or the rows' four flag bytes.
 template <int MODE>
@@ -57,12 +44,6 @@ struct TileRegs {
     u32x4 v[MODE == kModeIndex ? 1 : kRows];
     unsigned m[MODE == kModePred ? 1 : kRows];
 };
-
-// A typed pointer `bytes` past a block-uniform base: the 32-bit byte offset keeps the address a scalar base plus one VGPR.
-template <class T>
-__device__ __forceinline__ const T* at(const void* base, unsigned bytes) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + bytes);
-}
 
 // Elements and flag bytes at or past n are never read.
 template <int MODE>
@@ -161,26 +142,7 @@ __device__ __forceinline__ unsigned long long keep_bits(const TileRegs<MODE>& t,
             bits |= (unsigned long long)k << (4 * r);
         }
     }
-    if ((tile + 1) * kTileElems > n) {  // block-uniform: the last tile drops every element at or past n
-        const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-        const int rem = (int)(n - tile * kTileElems);  // elements of this tile below n (1 .. kTileElems - 1)
-        const int base = wave * kWaveItems + lane * 4;
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const int left = rem - (base + r * 256);  // elements of this lane's row below n
-            const unsigned ok = left >= 4 ? 0xfu : (left <= 0 ? 0u : ((1u << left) - 1u));
-            bits &= ~((unsigned long long)(0xfu & ~ok) << (4 * r));
-        }
-    }
-    return bits;
-}
-
-// A look-back that ran out of spins: marks the result invalid in the workspace and in the caller's sticky word.
-__device__ __forceinline__ void report_timeout(SelectWs* ws, unsigned* err_flag) {
-    if (pcmx::lane_id() == 0) {
-        atomicExch(&ws->timeout, 1u);
-        if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    return drop_past_n(bits, n, tile);
 }
 
 // Counts tile `tile` held in t, publishes its count, issues the loads of `next` into tn, looks back, stores.
@@ -194,29 +156,15 @@ __device__ __forceinline__ void finish_tile(const unsigned* __restrict__ x, cons
     const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
     // ---- keep bits, then per row the integer wave prefix of the kept elements (input order: row, lane, element)
     const unsigned long long bits = keep_bits<MODE>(t, op, thr, n, tile);
-    unsigned carry = 0u;  // wave-uniform: kept elements of the rows before r
+    unsigned carry;  // wave-uniform: the wave's kept elements
     unsigned lane_off[kRows];
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const unsigned k = (unsigned)(bits >> (4 * r)) & 0xfu;
-        const unsigned long long b0 = __ballot(k & 1u), b1 = __ballot(k & 2u), b2 = __ballot(k & 4u), b3 = __ballot(k & 8u);
-        lane_off[r] = lanes_below(b3, lanes_below(b2, lanes_below(b1, lanes_below(b0, carry))));
-        carry += (unsigned)(__popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3));
-        // the offset is materialised here: left to the compiler it sinks to the staging loop and keeps all 64 ballots
-        // (128 SGPRs) alive across the look-back
-        asm volatile("" : "+v"(lane_off[r]));
-    }
+    rank_rows(bits, lane_off, carry);
     if (lane == 0) s_wave_tot[wave] = carry;
     __syncthreads();
-    unsigned agg = 0u, wexcl = 0u;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const unsigned c = s_wave_tot[w];
-        wexcl += w < wave ? c : 0u;
-        agg += c;
-    }
+    unsigned agg, wexcl;
+    fold_wave_totals(s_wave_tot, agg, wexcl);
     if (threadIdx.x == 0)
-        __hip_atomic_store(&status[tile], pack(tile == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
+        __hip_atomic_store(&status[tile], Granule::pack(tile == 0 ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     // ---- the next tile's loads go out now and overlap the look-back below; in value mode this tile's payload stays
     //      in t until it is staged
@@ -227,41 +175,8 @@ __device__ __forceinline__ void finish_tile(const unsigned* __restrict__ x, cons
 
     // ---- wave 0: decoupled look-back over the predecessors' {flag, count} granules
     if (wave == 0) {
-        unsigned prefix = 0u;
-        if (tile != 0) {
-            long long look = tile - 1;  // newest predecessor still to account for
-            unsigned spins = 0;
-            while (true) {
-                const long long idx = look - lane;
-                const unsigned long long sv =
-                    idx >= 0 ? __hip_atomic_load(&status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : pack(kFlagIncl, 0u);
-                const unsigned flag = (unsigned)(sv >> 32);
-                const unsigned val = (unsigned)sv;
-                const unsigned long long m_incl = __ballot(flag == kFlagIncl);
-                const unsigned long long m_zero = __ballot(flag == 0u);
-                if (m_incl != 0ull) {
-                    const int first = __builtin_ctzll(m_incl);
-                    const unsigned long long need = (first == 63) ? ~0ull : ((1ull << (first + 1)) - 1ull);
-                    if ((m_zero & need) == 0ull) {
-                        prefix += pcmx::wave_reduce<unsigned, 0>(lane <= first ? val : 0u);
-                        break;
-                    }
-                } else if (m_zero == 0ull) {
-                    prefix += pcmx::wave_reduce<unsigned, 0>(val);
-                    look -= kWave;
-                    continue;
-                }
-                if (++spins > kSpinLimit) {  // bounded spin: report (workspace + sticky caller word) and fall through
-                    report_timeout(ws, err_flag);  // (a partial prefix is <= the true one: the stores stay inside out)
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (lane == 0)
-                __hip_atomic_store(&status[tile], pack(kFlagIncl, prefix + agg), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
+        // (after a give-up the partial prefix is <= the true one: the stores stay inside out)
+        const unsigned prefix = pcmx::lookback_publish<Granule>(ws, status, tile, agg, err_flag);
         if (lane == 0) {
             *s_prefix = prefix;
             if (tile == ntiles - 1) *count_dev = (long long)(prefix + agg);  // the owner of the last tile
@@ -340,16 +255,7 @@ __global__ __launch_bounds__(kWaves * kWave) void select_kernel(const unsigned* 
 
 inline long long num_tiles(long long n) { return (n + kTileElems - 1) / kTileElems; }
 // header + one granule per tile, padded to a multiple of 16 bytes (the whole block is zeroed before every launch)
-inline size_t ws_bytes(long long tiles) { return sizeof(SelectWs) + (size_t)((tiles + 1) & ~1LL) * 8; }
-
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
+inline size_t ws_bytes(long long tiles) { return sizeof(SelectWs) + (size_t)pcmx::pad2(tiles) * 8; }
 
 template <int MODE, bool kIndexOut>
 int launch(const void* x, const void* mask, void* out, long long n, int op, float thr, long long* count_dev,

@@ -29,6 +29,7 @@
 #include "pcmx_hip.h"
 
 namespace {
+using pcmx::device_cus;
 using pcmx::kWave;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) float lds_float;
@@ -586,15 +587,6 @@ int launch_rs(const float* A, const float* B, float* Cm, int M, int N, int K, in
         sgemm_rs_kernel<false><<<grid, C::kThreads, 0, s>>>(A, B, Cm, M, N, K, lda, ldb, ldc, alpha, beta);
     return (int)hipGetLastError();
 }
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
-
 // max_blocks <= 0: one block per CU
 int launch_direct(const float* A, const float* B, float* Cm, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
                   float beta, int max_blocks, hipStream_t s) {

@@ -16,18 +16,30 @@
 //    so the stores of a run are contiguous. Values travel with their keys through a second LDS array.
 //  * Flag state: every pass has its own ticket and its own granule array; one hipMemsetAsync in front of the histogram
 //    kernel zeroes the header, the histograms and the granules of all passes that run (1 KiB per tile and pass).
-//  * Bounded spins and the give-up report are the scan's (ws->timeout and the caller's sticky error word).
+//  * The spin bound and the give-up report are lookback.h's (ws->head.timeout and the caller's sticky error word); the
+//    per-digit loop and its 4-byte granules are this file's own.
 // Keys live in the ping-pong buffers TRANSFORMED (u32 order = wanted order): the transform is applied in registers to
 // what the first pass loads, and inverted in what the last pass stores.
+#include "lookback.h"
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "radix_key.h"
 
 namespace {
+using pcmx::align16;
+using pcmx::device_cus;
+using pcmx::from_key;
+using pcmx::kFlagAgg;
+using pcmx::kFlagIncl;
+using pcmx::kSpinLimit;
 using pcmx::kWave;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using pcmx::misaligned;
+using pcmx::report_timeout;
+using pcmx::to_key;
+using pcmx::u32x4;
 
-constexpr unsigned kFlagAgg = 1u, kFlagIncl = 2u, kFlagShift = 30, kCountMask = (1u << kFlagShift) - 1u;
-constexpr unsigned kSpinLimit = 1u << 26;
+// this file's granules are 4-byte words {flag: 2, count: 30}, one per digit and tile
+constexpr unsigned kFlagShift = 30, kCountMask = (1u << kFlagShift) - 1u;
 constexpr int kWaves = 8, kThreads = kWaves * kWave;  // 512
 constexpr int kRows = 32;                             // keys per lane
 constexpr int kWaveItems = kRows * kWave;             // 2048 contiguous keys per wave
@@ -36,37 +48,15 @@ constexpr int kDigits = 256, kMaxPasses = 4;
 constexpr int kLook = 32;                             // predecessors per look-back poll and digit
 constexpr long long kMaxN = (1LL << kFlagShift) - 1;  // a granule's count field carries an inclusive prefix <= n
 
-// The first 16 bytes are the scan's workspace header, so pcmx_scan_check reads a sort workspace too (`ticket` itself
-// is unused here: every pass has its own).
 struct SortWs {
-    unsigned ticket;
-    unsigned timeout;
-    unsigned pad[2];
+    pcmx::LookbackHeader head;  // its `ticket` is unused here: every pass has its own
     unsigned pass_ticket[kMaxPasses];
     unsigned hist[kMaxPasses][kDigits];
     // followed by unsigned status[passes][num_tiles][256], then the ping-pong buffers
 };
-
-// Raw bits -> key whose unsigned order is the wanted order (flip = ~0 for descending).
-__device__ __forceinline__ unsigned to_key(unsigned b, int type, unsigned flip) {
-    unsigned k = b;
-    if (type == PCMX_KEY_F32) {
-        const unsigned a = b & 0x7fffffffu;
-        k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-        if (a == 0u) k = 0x80000000u;          // -0.0 == +0.0
-        if (a > 0x7f800000u) k = 0xffffffffu;  // every NaN: one key, above +inf
-    } else if (type == PCMX_KEY_I32) {
-        k = b ^ 0x80000000u;
-    }
-    return k ^ flip;
-}
-
-__device__ __forceinline__ unsigned from_key(unsigned k, int type, unsigned flip) {
-    k ^= flip;
-    if (type == PCMX_KEY_F32) return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    if (type == PCMX_KEY_I32) return k ^ 0x80000000u;
-    return k;
-}
+static_assert(offsetof(SortWs, head) == 0 && offsetof(SortWs, pass_ticket) == 16 && offsetof(SortWs, hist) == 32 &&
+                  sizeof(SortWs) == 32 + kMaxPasses * kDigits * 4,
+              "the workspace layout is part of the C interface (pcmx_sort_workspace_bytes)");
 
 __device__ __forceinline__ unsigned cnt_load(const unsigned* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -161,11 +151,6 @@ struct PassArgs {
     int first, last;       // transform on load / invert on store
     int iota;              // values of this pass are the global indices (first pass of an argsort)
 };
-
-__device__ __forceinline__ void report_timeout(SortWs* ws, unsigned* err_flag) {
-    atomicExch(&ws->timeout, 1u);
-    if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // Issues the loads of one tile: key[r] / val[r] = element tile * 16384 + wave * 2048 + r * 64 + lane. Nothing at or
 // past n is read (those registers hold 0 and are never ranked or staged).
@@ -326,7 +311,7 @@ __global__ __launch_bounds__(kThreads) void sort_pass_kernel(const unsigned* __r
                         // partial prefix is never larger than the true one, and base[d] comes from the complete
                         // histogram, so every store below stays inside [0, n) of the output buffers.
                         if (++spins > kSpinLimit) {
-                            report_timeout(ws, err_flag);
+                            report_timeout(&ws->head, err_flag);  // from whichever thread gave up
                             break;
                         }
                         __builtin_amdgcn_s_sleep(1);
@@ -359,22 +344,10 @@ __global__ __launch_bounds__(kThreads) void sort_pass_kernel(const unsigned* __r
 }
 
 inline long long num_tiles(long long n) { return (n + kTileElems - 1) / kTileElems; }
-inline size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 // One ping-pong buffer of n words plus an odd number of 256-byte lines, so that the keys and values a tile reads and
 // writes together do not sit a power of two apart in the workspace.
 inline size_t buf_bytes(long long n) { return align16((size_t)n * 4u) + 273u * 256u; }
 inline size_t status_bytes(long long tiles) { return (size_t)tiles * kDigits * sizeof(unsigned); }
-
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
-
-bool misaligned(const void* p) { return (((uintptr_t)p) & 15u) != 0; }
 }  // namespace
 
 // header | granules of 4 passes | key buffer A | key buffer B (index mode: the keys may never touch a caller buffer) |

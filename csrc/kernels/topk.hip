@@ -2,7 +2,7 @@
 // No counterpart in the reference programs: a library addition, the next member of the scan / select / sort family.
 //
 // The result is the first k entries of sort.hip's stable sort (values and int32 flat indices), found without moving
-// the data: keys are compared TRANSFORMED exactly as in sort.hip (to_key below is a local copy; flip = ~0 when the
+// the data: keys are compared TRANSFORMED exactly as in sort.hip (radix_key.h's to_key, shared; flip = ~0 when the
 // largest are wanted), so "better" always means "smaller transformed key" and the k best are the k smallest.
 //  * Step A, the k-th key T: four passes over the keys, 8 bits per digit from the top. A pass histograms the current
 //    digit of the keys whose higher digits equal the prefix chosen so far (256 LDS counters per block, sort.hip's
@@ -12,7 +12,7 @@
 //    live in the workspace; the choice never goes through the host and kernel boundaries alone order the passes: no
 //    inter-block waiting in step A. After the last pass the workspace holds T, c_beyond (keys better than T, < k) and
 //    need_eq = k - c_beyond (>= 1). The k-th value is this step plus one store of from_key(T).
-//  * Step B, the ordered gather: one pass on select.hip's protocol (copied, not generalised): one 512-thread block per
+//  * Step B, the ordered gather: one pass on select.hip's schedule and lookback.h's look-back: one 512-thread block per
 //    CU, 32768-key tiles claimed from the atomic ticket, the next tile's loads in flight during the look-back, 8-byte
 //    granules written with one relaxed agent-scope store, bounded spins, hipMemsetAsync of the flags before the launch.
 //    The granule carries TWO counts, {flag: 2 bits, keys better than T: 31, keys equal to T: 31}, because which ties are
@@ -23,31 +23,37 @@
 //    Every store is guarded by pos < k, so a look-back that gave up (a prefix too small) cannot write outside.
 //  * Step C (sorted output): the k survivors, in ascending index order, are sorted as (value, index) pairs by sort.hip's
 //    stable pcmx_radix_sort, which yields exactly the prefix of the full stable sort.
-// The workspace header has the scan's layout, so pcmx_scan_check reads a top-k workspace too; a give-up sets
+// The workspace begins with pcmx::LookbackHeader, so pcmx_scan_check reads a top-k workspace too; a give-up sets
 // ws->timeout and ORs 1 into the caller's sticky error word.
+#include "lookback.h"
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "radix_key.h"
 
 namespace {
+using pcmx::align16;
+using pcmx::at;
+using pcmx::device_cus;
+using pcmx::from_key;
+using pcmx::kFlagAgg;
+using pcmx::kFlagIncl;
 using pcmx::kWave;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using pcmx::lanes_below;
+using pcmx::misaligned;
+using pcmx::to_key;
+using pcmx::u32x4;
 typedef unsigned long long u64;
+typedef pcmx::GranuleU31x2 Granule;  // {keys better than T, keys equal to T}
 
-constexpr unsigned kFlagAgg = 1u, kFlagIncl = 2u;
-constexpr unsigned kSpinLimit = 1u << 26;
-constexpr u64 kCountMask = (1ull << 31) - 1ull;
 constexpr int kRows = 16, kWaves = 8, kThreads = kWaves * kWave;  // 16 rows of 4 keys per lane, 8 waves
 constexpr int kWaveItems = kRows * 4 * kWave;                     // 4096 contiguous keys per wave
 constexpr int kTileElems = kWaves * kWaveItems;                   // 32768 (128 KiB of keys)
 constexpr int kDigits = 256, kPasses = 4;
 constexpr long long kMaxN = (1LL << 30) - 1;                      // the sort's limit; granule counts have 31 bits
 
-// The first 16 bytes are the scan's workspace header. The whole struct and the granules behind it are zeroed by one
-// hipMemsetAsync in front of the first kernel.
+// The whole struct and the granules behind it are zeroed by one hipMemsetAsync in front of the first kernel.
 struct TopkWs {
-    unsigned ticket;
-    unsigned timeout;
-    unsigned pad[2];
+    pcmx::LookbackHeader head;
     unsigned prefix;    // the digits of T chosen so far (lower bits 0); T itself after the last pass
     unsigned k_rem;     // 1-based rank of the k-th key among the keys that match the prefix; need_eq after the last pass
     unsigned c_beyond;  // keys strictly better than every key that matches the prefix
@@ -55,27 +61,10 @@ struct TopkWs {
     unsigned hist[kPasses][kDigits];
     // followed by u64 status[num_tiles]
 };
-
-// Raw bits -> key whose unsigned order is the wanted order (local copy of sort.hip's; flip = ~0 for descending).
-__device__ __forceinline__ unsigned to_key(unsigned b, int type, unsigned flip) {
-    unsigned k = b;
-    if (type == PCMX_KEY_F32) {
-        const unsigned a = b & 0x7fffffffu;
-        k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-        if (a == 0u) k = 0x80000000u;          // -0.0 == +0.0
-        if (a > 0x7f800000u) k = 0xffffffffu;  // every NaN: one key, above +inf
-    } else if (type == PCMX_KEY_I32) {
-        k = b ^ 0x80000000u;
-    }
-    return k ^ flip;
-}
-
-__device__ __forceinline__ unsigned from_key(unsigned k, int type, unsigned flip) {
-    k ^= flip;
-    if (type == PCMX_KEY_F32) return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    if (type == PCMX_KEY_I32) return k ^ 0x80000000u;
-    return k;
-}
+static_assert(offsetof(TopkWs, head) == 0 && offsetof(TopkWs, prefix) == 16 && offsetof(TopkWs, k_rem) == 20 &&
+                  offsetof(TopkWs, c_beyond) == 24 && offsetof(TopkWs, hist) == 32 &&
+                  sizeof(TopkWs) == 32 + kPasses * kDigits * 4,
+              "the workspace layout is part of the C interface (pcmx_topk_workspace_bytes)");
 
 // ---------------------------------------------------------------- step A: one histogram pass
 // Digit `pass` (0 = bits 31..24) of the keys whose higher digits equal ws->prefix. Reads the keys once and writes
@@ -153,19 +142,6 @@ __global__ __launch_bounds__(kDigits) void topk_choose_kernel(TopkWs* ws, int pa
 }
 
 // ---------------------------------------------------------------- step B: the ordered gather
-__device__ __forceinline__ u64 pack(unsigned flag, unsigned beyond, unsigned equal) {
-    return ((u64)flag << 62) | ((u64)beyond << 31) | (u64)equal;
-}
-
-__device__ __forceinline__ unsigned lanes_below(u64 ballot, unsigned acc) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, acc));
-}
-
-template <class T>
-__device__ __forceinline__ const T* at(const void* base, unsigned bytes) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + bytes);
-}
-
 struct TileRegs {
     u32x4 v[kRows];
 };
@@ -208,13 +184,6 @@ __device__ __forceinline__ unsigned classify(const u32x4& v, unsigned flip, unsi
     return m;
 }
 
-__device__ __forceinline__ void report_timeout(TopkWs* ws, unsigned* err_flag) {
-    if (pcmx::lane_id() == 0) {
-        atomicExch(&ws->timeout, 1u);
-        if (err_flag) __hip_atomic_fetch_or(err_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
 // Counts tile `tile` held in t, publishes its two counts, issues the loads of `next` into tn, looks back, stores.
 template <int TYPE>
 __device__ __forceinline__ void finish_tile(const unsigned* __restrict__ x, unsigned* __restrict__ vals,
@@ -247,54 +216,21 @@ __device__ __forceinline__ void finish_tile(const unsigned* __restrict__ x, unsi
         wexb += w < wave ? b : 0u, wexe += w < wave ? e : 0u;
         aggb += b, agge += e;
     }
+    const pcmx::Count2 agg = {aggb, agge};
     if (threadIdx.x == 0)
-        __hip_atomic_store(&status[tile], pack(tile == 0u ? kFlagIncl : kFlagAgg, aggb, agge), __ATOMIC_RELAXED,
+        __hip_atomic_store(&status[tile], Granule::pack(tile == 0u ? kFlagIncl : kFlagAgg, agg), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     // ---- the next tile's loads go out now and overlap the look-back below; this tile's keys stay in t
     if (next < ntiles) load_tile(x, n, next, tn);
     // ---- the ticket for the tile after `next`, taken before this tile's stores (as in the scan)
     unsigned ticket = 0u;
-    if (threadIdx.x == 0) ticket = atomicAdd(&ws->ticket, 1u);
+    if (threadIdx.x == 0) ticket = atomicAdd(&ws->head.ticket, 1u);
 
     // ---- wave 0: decoupled look-back over the predecessors' {flag, better, equal} granules
     if (wave == 0) {
-        unsigned pb = 0u, pe = 0u;
-        if (tile != 0u) {
-            long long look = (long long)tile - 1;  // newest predecessor still to account for
-            unsigned spins = 0;
-            while (true) {
-                const long long i = look - lane;
-                const u64 sv = i >= 0 ? __hip_atomic_load(&status[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                      : pack(kFlagIncl, 0u, 0u);
-                const unsigned flag = (unsigned)(sv >> 62);
-                const unsigned vb = (unsigned)((sv >> 31) & kCountMask), ve = (unsigned)(sv & kCountMask);
-                const u64 m_incl = __ballot(flag == kFlagIncl);
-                const u64 m_zero = __ballot(flag == 0u);
-                if (m_incl != 0ull) {
-                    const int first = __builtin_ctzll(m_incl);
-                    const u64 need = (first == 63) ? ~0ull : ((1ull << (first + 1)) - 1ull);
-                    if ((m_zero & need) == 0ull) {
-                        pb += pcmx::wave_reduce<unsigned, 0>(lane <= first ? vb : 0u);
-                        pe += pcmx::wave_reduce<unsigned, 0>(lane <= first ? ve : 0u);
-                        break;
-                    }
-                } else if (m_zero == 0ull) {
-                    pb += pcmx::wave_reduce<unsigned, 0>(vb);
-                    pe += pcmx::wave_reduce<unsigned, 0>(ve);
-                    look -= kWave;
-                    continue;
-                }
-                if (++spins > kSpinLimit) {  // bounded spin: report (workspace + sticky caller word) and fall through
-                    report_timeout(ws, err_flag);  // (partial prefixes are <= the true ones; stores are guarded by pos < k)
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (lane == 0)
-                __hip_atomic_store(&status[tile], pack(kFlagIncl, pb + aggb, pe + agge), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0) s_prefix[0] = pb, s_prefix[1] = pe;
+        // (after a give-up the partial prefixes are <= the true ones; stores are guarded by pos < k)
+        const pcmx::Count2 p = pcmx::lookback_publish<Granule>(&ws->head, status, tile, agg, err_flag);
+        if (lane == 0) s_prefix[0] = p.x, s_prefix[1] = p.y;
     }
     if (threadIdx.x == 0) *s_next = ticket;
     __syncthreads();
@@ -353,8 +289,8 @@ __global__ __launch_bounds__(kThreads) void topk_gather_kernel(const unsigned* _
     __shared__ unsigned s_tile[2];
     TileRegs ta_regs, tb_regs;
     if (threadIdx.x == 0) {
-        s_tile[0] = atomicAdd(&ws->ticket, 1u);
-        s_tile[1] = atomicAdd(&ws->ticket, 1u);
+        s_tile[0] = atomicAdd(&ws->head.ticket, 1u);
+        s_tile[1] = atomicAdd(&ws->head.ticket, 1u);
     }
     __syncthreads();
     const unsigned T = ws->prefix, need_eq = ws->k_rem;  // step A's result (earlier kernels of this stream)
@@ -377,20 +313,8 @@ __global__ __launch_bounds__(kThreads) void topk_gather_kernel(const unsigned* _
 }
 
 inline long long num_tiles(long long n) { return (n + kTileElems - 1) / kTileElems; }
-inline size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 // header, histograms and one granule per tile, padded to a multiple of 16 bytes: the block zeroed before every call
-inline size_t flag_bytes(long long tiles) { return sizeof(TopkWs) + (size_t)((tiles + 1) & ~1LL) * 8; }
-
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
-
-bool misaligned(const void* p) { return (((uintptr_t)p) & 15u) != 0; }
+inline size_t flag_bytes(long long tiles) { return sizeof(TopkWs) + (size_t)pcmx::pad2(tiles) * 8; }
 
 int check_args(const void* keys, long long n, long long k, long long k_min, int key_type, const void* workspace) {
     if (n <= 0 || n > kMaxN || k < k_min || k > n) return PCMX_ERR_ARG;

@@ -21,6 +21,7 @@
 #include "pcmx_hip.h"
 
 namespace {
+using pcmx::device_cus;
 using pcmx::kWave;
 constexpr int kThreads = 256;  // grid-stride fallback and the small kernels
 constexpr int kUnroll = 4;
@@ -241,15 +242,6 @@ inline int stream_grid(long long n, int per_thread) {
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-int device_cus() {  // cached per device (no attribute query on the launch path)
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 256;
-    return cus[dev] > 0 ? cus[dev] : 256;
-}
 
 // The self-resetting counter pair of (device, stream), allocated and zeroed on first use (kept for the process);
 // nullptr while `s` is capturing (the caller then launches the grid-stride form).

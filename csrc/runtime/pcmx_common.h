@@ -24,6 +24,7 @@ namespace pcmx {
 // Native clang vectors (HIP's float4 is a struct the nontemporal builtins reject).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <class V>
 __device__ __forceinline__ V ld_nt(const V* p) { return __builtin_nontemporal_load(p); }
 template <class V>
@@ -77,6 +78,22 @@ __device__ __forceinline__ float wave_from_next(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
 }
 
+// The same shift for a 32-bit pattern: lane l gets lane l-1's value (DPP wave_shr:1); lane 0 gets 0.
+__device__ __forceinline__ unsigned from_lane_below(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
+}
+
+// u32 wave prefix of one-bit items: acc + how many lanes BELOW this one have their bit set in the ballot (v_mbcnt).
+__device__ __forceinline__ unsigned lanes_below(unsigned long long ballot, unsigned acc) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, acc));
+}
+
+// A typed pointer `bytes` past a block-uniform base: the 32-bit byte offset keeps the address a scalar base plus one VGPR.
+template <class T>
+__device__ __forceinline__ const T* at(const void* base, unsigned bytes) {
+    return reinterpret_cast<const T*>(static_cast<const char*>(base) + bytes);
+}
+
 // Inclusive wave scan (Hillis-Steele over 64 lanes).
 __device__ __forceinline__ float wave_inclusive_scan(float v) {
     const int l = lane_id();
@@ -99,5 +116,24 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // Streaming grid cap (256 CUs x 64 blocks, then grid-stride): at 1e9 f32 a 16384-block grid streams 5.5 TB/s for
 // vadd / copy / fill against 4.8-5.1 with 2048 (scripts/stream_bw_lab.hip, profiles/r4_bench/stream_bw_lab.txt)
 inline int grid_cap_streaming() { return 256 * 64; }
+
+// Compute units of the current device, cached per device (no attribute query on the launch path); 256 when the
+// query fails. Inline, not in the device runtime: every library built from a kernel source carries it, the test-only
+// fault-injection build of scan.hip included.
+inline int device_cus() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        cus[dev] = 256;
+    return cus[dev] > 0 ? cus[dev] : 256;
+}
+
+// Workspace layout helpers: a count padded to a multiple of 2 / 4 entries, a byte size padded to 16, and the
+// alignment check of the launchers (16 bytes unless a mask is given).
+__host__ __device__ inline long long pad2(long long t) { return (t + 1) & ~1LL; }
+__host__ __device__ inline long long pad4(long long t) { return (t + 3) & ~3LL; }
+inline size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+inline bool misaligned(const void* p, unsigned mask = 15u) { return (((uintptr_t)p) & mask) != 0; }
 
 }  // namespace pcmx
