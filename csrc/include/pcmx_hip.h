@@ -229,6 +229,46 @@ int pcmx_hist_even_f32(const float* x, long long n, long long num_bins, float lo
 int pcmx_hist_range_f32(const float* x, long long n, const float* edges, long long num_bins, int32_t* out,
                         int accumulate, hipStream_t s);
 
+/* ---------------------------------------------------------------- merge of sorted sequences / sorted search */
+/* Merges two SORTED sequences of 32-bit keys (na and nb keys, either may be empty) into one of na + nb keys, and
+ * searches sorted keys, on the merge-path diagonal partition (csrc/kernels/merge.hip). Keys are compared only through
+ * pcmx_radix_sort's TRANSFORMED key (U32 identity; I32 k ^ 0x80000000; F32 -0.0 == +0.0 and every NaN one key above
+ * +inf), reversed for descending != 0, and are moved as their raw 32 bits: the transform is never inverted, so NaN
+ * payloads and the sign of zero come out as they went in. "Sorted" means non-decreasing in that order. It is a
+ * precondition and is not checked: with unsorted input the result is unspecified, but every load and store stays
+ * inside the given buffers. A tie goes to a: an element of a precedes an equal element of b, so the result is the
+ * stable sort of the concatenation a ++ b. Values are 4 bytes moved as bits.
+ *   PCMX_MERGE_KEYS   keys_out = merged keys; vals_a / vals_b / vals_or_idx_out unused
+ *   PCMX_MERGE_PAIRS  keys_out, vals_or_idx_out = keys and their values
+ *   PCMX_MERGE_INDEX  vals_or_idx_out[j] = int32 index into the concatenation of the j-th key (i for a[i], na + i for
+ *                     b[i]); keys_out may be NULL (no keys are written)
+ * Two launches: a partition kernel (one thread per output tile writes where the tile starts in a: ntiles + 1 int32
+ * values in the workspace) and a merge kernel (one block per tile, through LDS). No block waits for another, there are
+ * no atomics and no err_flag; the outputs are the same on every call. The inputs are never written and need only 4-B
+ * alignment; outputs and the workspace (pcmx_merge_workspace_bytes, one call in flight per workspace) are 16-B
+ * aligned; no output may overlap an input; na + nb < 2^31. A bad key type, mode, alignment or size, or a missing
+ * pointer, returns PCMX_ERR_ARG and launches nothing; na + nb == 0 returns 0 and touches nothing. */
+enum { PCMX_MERGE_KEYS = 0, PCMX_MERGE_PAIRS = 1, PCMX_MERGE_INDEX = 2 };
+long long pcmx_merge_workspace_bytes(long long na, long long nb);
+int pcmx_merge_b32(const void* keys_a, const void* vals_a, long long na, const void* keys_b, const void* vals_b,
+                   long long nb, void* keys_out, void* vals_or_idx_out, int key_type, int mode, int descending,
+                   void* workspace, hipStream_t s);
+/* out[i] (int32, i < m) = the number of the n sorted keys that precede needles[i] (right == 0: a lower bound), or
+ * that precede or equal it (right != 0: an upper bound), in the order above: torch.searchsorted, except that a NaN
+ * needle ties with the NaNs at the end of the keys. Needles may be in any order: a block stages evenly spaced keys in
+ * LDS (all of them up to 8192), a lane bounds its needle among those and finishes in the one interval left in global
+ * memory, with the same predicate at both levels. needles_sorted != 0 is the caller's promise that the needles are
+ * sorted in the same order: with n + m < 2^31 and 8 m >= n (fewer needles are cheaper to search one by one than the
+ * keys are to read) the search then runs as a merge of needles and keys that writes no keys (the partition and merge
+ * kernels above; right != 0 gives ties to the keys), bandwidth-bound and load-balanced, with results bit-identical to
+ * the general route when the promise holds and unspecified (but in bounds) when it does not.
+ * n == 0 writes zeros. sorted_keys and needles 4-B aligned, out and the workspace
+ * (pcmx_searchsorted_workspace_bytes, one call in flight per workspace) 16-B aligned, n and m < 2^31, out must not
+ * overlap an input (else PCMX_ERR_ARG, nothing launched); m == 0 returns 0 and touches nothing. */
+long long pcmx_searchsorted_workspace_bytes(long long n, long long m, int needles_sorted);
+int pcmx_searchsorted_b32(const void* sorted_keys, long long n, const void* needles, long long m, int32_t* out,
+                          int key_type, int right, int descending, int needles_sorted, void* workspace, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

@@ -678,6 +678,133 @@ at::Tensor hist_range(const at::Tensor& x, const at::Tensor& edges, const c10::o
     return hist_finish(d, out);
 }
 
+// ---------------------------------------------------------------- merge of sorted sequences / sorted search
+// Merge of two sorted float32 / int32 key sequences, flattened, and searchsorted (csrc/kernels/merge.hip). The inputs
+// keep their element-aligned start (a view such as x[1:] is not copied; only a non-contiguous input is gathered
+// first). Outputs are fresh 1-D tensors, or the caller's `out` tensors (contiguous, exact size, right dtype; one that is
+// not 16-B aligned is written through a temporary). Workspace from the caching allocator, no host synchronisation, no
+// error word: no block of these kernels waits for another.
+at::Tensor merge_input(const at::Tensor& t, const at::Tensor& like, const char* what, const char* name) {
+    TORCH_CHECK(t.device() == like.device(), what, ": ", name, " must be on ", like.device());
+    TORCH_CHECK(t.scalar_type() == like.scalar_type(), what, ": ", name, " has dtype ", t.scalar_type(), ", expected ",
+                like.scalar_type());
+    return t.contiguous().view(-1);
+}
+
+at::Tensor merge_dest(const c10::optional<at::Tensor>& out, const at::Tensor& like, at::ScalarType dt, int64_t n,
+                      const char* what) {
+    if (!(out.has_value() && out->defined())) return at::empty({n}, like.options().dtype(dt));
+    check_gpu(*out, "out", dt);
+    TORCH_CHECK(out->device() == like.device() && out->is_contiguous() && out->numel() == n, what,
+                ": out must be contiguous, on the input's device, with ", n, " elements");
+    return (reinterpret_cast<uintptr_t>(out->data_ptr()) & 15u) ? at::empty({n}, out->options()) : out->view(-1);
+}
+
+at::Tensor merge_finish(const c10::optional<at::Tensor>& out, const at::Tensor& dest) {
+    if (!(out.has_value() && out->defined())) return dest;
+    if (dest.data_ptr() != out->data_ptr()) out->view(-1).copy_(dest);
+    return *out;
+}
+
+// keys_out / aux_out: destinations or undefined tensors (no such output in this mode)
+void merge_launch(const at::Tensor& a, const at::Tensor& b, const at::Tensor* va, const at::Tensor* vb,
+                  at::Tensor keys_out, at::Tensor aux_out, int mode, bool descending, const char* what) {
+    const int key_type = sort_key_type(a, what);
+    const int64_t na = a.numel(), nb = b.numel();
+    if (na + nb == 0) return;
+    at::Tensor ac = a, bc = b, vac, vbc;
+    for (const at::Tensor* o : {&keys_out, &aux_out}) {
+        if (!o->defined()) continue;
+        if (overlaps(ac, *o)) ac = ac.clone();
+        if (overlaps(bc, *o)) bc = bc.clone();
+    }
+    if (va) {
+        vac = *va, vbc = *vb;
+        for (const at::Tensor* o : {&keys_out, &aux_out}) {
+            if (overlaps(vac, *o)) vac = vac.clone();
+            if (overlaps(vbc, *o)) vbc = vbc.clone();
+        }
+    }
+    auto ws = workspace(a, pcmx_merge_workspace_bytes(na, nb));
+    check_rc(pcmx_merge_b32(ac.data_ptr(), va ? vac.data_ptr() : nullptr, na, bc.data_ptr(), va ? vbc.data_ptr() : nullptr,
+                            nb, keys_out.defined() ? keys_out.data_ptr() : nullptr,
+                            aux_out.defined() ? aux_out.data_ptr() : nullptr, key_type, mode, descending ? 1 : 0,
+                            ws.data_ptr(), cur_stream(a)),
+             what);
+}
+
+int64_t merge_total(const at::Tensor& a, const at::Tensor& b, const char* what) {
+    const int64_t n = a.numel() + b.numel();
+    TORCH_CHECK(n < (1LL << 31), what, ": indices are int32, the two inputs together must have fewer than 2^31 elements");
+    return n;
+}
+
+at::Tensor merge_keys(const at::Tensor& a, const at::Tensor& b, bool descending, const c10::optional<at::Tensor>& out) {
+    sort_key_type(a, "merge_keys");
+    const at::DeviceGuard g(a.device());
+    at::Tensor ac = a.contiguous().view(-1), bc = merge_input(b, a, "merge_keys", "b");
+    at::Tensor dest = merge_dest(out, a, a.scalar_type(), merge_total(a, b, "merge_keys"), "merge_keys");
+    merge_launch(ac, bc, nullptr, nullptr, dest, at::Tensor(), PCMX_MERGE_KEYS, descending, "merge_keys");
+    return merge_finish(out, dest);
+}
+
+// (merged keys, int32 indices into cat(a, b)); with want_keys false the first tensor is empty and no keys are written
+std::tuple<at::Tensor, at::Tensor> merge_index(const at::Tensor& a, const at::Tensor& b, bool descending, bool want_keys,
+                                               const c10::optional<at::Tensor>& out_keys,
+                                               const c10::optional<at::Tensor>& out_idx) {
+    sort_key_type(a, "merge_index");
+    const at::DeviceGuard g(a.device());
+    at::Tensor ac = a.contiguous().view(-1), bc = merge_input(b, a, "merge_index", "b");
+    const int64_t n = merge_total(a, b, "merge_index");
+    at::Tensor kd = want_keys ? merge_dest(out_keys, a, a.scalar_type(), n, "merge_index") : at::Tensor();
+    at::Tensor id = merge_dest(out_idx, a, at::kInt, n, "merge_index");
+    merge_launch(ac, bc, nullptr, nullptr, kd, id, PCMX_MERGE_INDEX, descending, "merge_index");
+    return {want_keys ? merge_finish(out_keys, kd) : at::empty({0}, a.options()), merge_finish(out_idx, id)};
+}
+
+std::tuple<at::Tensor, at::Tensor> merge_pairs(const at::Tensor& ka, const at::Tensor& va, const at::Tensor& kb,
+                                               const at::Tensor& vb, bool descending,
+                                               const c10::optional<at::Tensor>& out_keys,
+                                               const c10::optional<at::Tensor>& out_values) {
+    sort_key_type(ka, "merge_pairs");
+    TORCH_CHECK(va.scalar_type() == at::kFloat || va.scalar_type() == at::kInt, "merge_pairs: values have dtype ",
+                va.scalar_type(), ", expected float32 or int32");
+    TORCH_CHECK(va.numel() == ka.numel() && vb.numel() == kb.numel(), "merge_pairs: ", va.numel(), " / ", vb.numel(),
+                " values for ", ka.numel(), " / ", kb.numel(), " keys");
+    const at::DeviceGuard g(ka.device());
+    at::Tensor kac = ka.contiguous().view(-1), kbc = merge_input(kb, ka, "merge_pairs", "keys_b");
+    TORCH_CHECK(va.device() == ka.device(), "merge_pairs: values_a must be on ", ka.device());
+    at::Tensor vac = va.contiguous().view(-1), vbc = merge_input(vb, va, "merge_pairs", "values_b");
+    const int64_t n = merge_total(ka, kb, "merge_pairs");
+    at::Tensor kd = merge_dest(out_keys, ka, ka.scalar_type(), n, "merge_pairs");
+    at::Tensor vd = merge_dest(out_values, ka, va.scalar_type(), n, "merge_pairs");
+    merge_launch(kac, kbc, &vac, &vbc, kd, vd, PCMX_MERGE_PAIRS, descending, "merge_pairs");
+    return {merge_finish(out_keys, kd), merge_finish(out_values, vd)};
+}
+
+// int32 [values.shape]: how many keys of the sorted sequence precede (right: precede or equal) each value
+at::Tensor searchsorted(const at::Tensor& sorted, const at::Tensor& values, bool right, bool descending,
+                        bool values_sorted, const c10::optional<at::Tensor>& out) {
+    const int key_type = sort_key_type(sorted, "searchsorted");
+    const at::DeviceGuard g(sorted.device());
+    at::Tensor sc = sorted.contiguous().view(-1), vc = merge_input(values, sorted, "searchsorted", "values");
+    const int64_t n = sc.numel(), m = vc.numel();
+    TORCH_CHECK(n < (1LL << 31) && m < (1LL << 31), "searchsorted: the sequence and the values must each have fewer than "
+                "2^31 elements");
+    const bool has_out = out.has_value() && out->defined();
+    if (has_out) TORCH_CHECK(out->sizes() == values.sizes(), "searchsorted: out must have the shape of values");
+    at::Tensor dest = merge_dest(out, sorted, at::kInt, m, "searchsorted");
+    if (m != 0) {
+        if (overlaps(sc, dest)) sc = sc.clone();
+        if (overlaps(vc, dest)) vc = vc.clone();
+        auto ws = workspace(sorted, pcmx_searchsorted_workspace_bytes(n, m, values_sorted ? 1 : 0));
+        check_rc(pcmx_searchsorted_b32(sc.data_ptr(), n, vc.data_ptr(), m, dest.data_ptr<int32_t>(), key_type, right ? 1 : 0,
+                                       descending ? 1 : 0, values_sorted ? 1 : 0, ws.data_ptr(), cur_stream(sorted)),
+                 "searchsorted");
+    }
+    return has_out ? merge_finish(out, dest) : dest.view(values.sizes());
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -1225,6 +1352,10 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("bincount(Tensor x, int num_bins, Tensor? weights=None, Tensor(a!)? out=None, bool accumulate=False) -> Tensor");
     m.def("hist_even(Tensor x, int bins, float lo, float hi, float scale, Tensor(a!)? out=None, bool accumulate=False) -> Tensor");
     m.def("hist_range(Tensor x, Tensor edges, Tensor(a!)? out=None, bool accumulate=False) -> Tensor");
+    m.def("merge_keys(Tensor a, Tensor b, bool descending=False, Tensor(a!)? out=None) -> Tensor");
+    m.def("merge_index(Tensor a, Tensor b, bool descending=False, bool want_keys=True, Tensor(a!)? out_keys=None, Tensor(b!)? out_idx=None) -> (Tensor, Tensor)");
+    m.def("merge_pairs(Tensor keys_a, Tensor values_a, Tensor keys_b, Tensor values_b, bool descending=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_values=None) -> (Tensor, Tensor)");
+    m.def("searchsorted(Tensor sorted_sequence, Tensor values, bool right=False, bool descending=False, bool values_sorted=False, Tensor(a!)? out=None) -> Tensor");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -1279,6 +1410,10 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("bincount", bincount);
     m.impl("hist_even", hist_even);
     m.impl("hist_range", hist_range);
+    m.impl("merge_keys", merge_keys);
+    m.impl("merge_index", merge_index);
+    m.impl("merge_pairs", merge_pairs);
+    m.impl("searchsorted", searchsorted);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

@@ -1189,9 +1189,126 @@ class Bincount(Workload):
                 "check_passed": ok}
 
 
+class Merge(Workload):
+    """Merge of two sorted key arrays, or a sorted search, over n keys per GPU in all (csrc/kernels/merge.hip). mode
+    "keys" (ops.merge_keys), "pairs" (ops.merge_by_key with an int32 payload), "index" (ops.merge: keys and int32
+    indices into the concatenation), "search" (ops.searchsorted, needles in random order) or "search_sorted" (sorted
+    needles, values_sorted=True). split is the fraction of n that is a (merge) or the needles (search), the rest is b /
+    the haystack; na and nb, when given, set the two sizes directly. dtype f32 (uniform in [-1, 1)) or i32 (full
+    range). dist: "interleaved" (both sides drawn from the same range), "disjoint" (every key of a below every key of
+    b) or "equal" (one key everywhere: every comparison is a tie). No communication (weak scaling)."""
+
+    MODES = ("keys", "pairs", "index", "search", "search_sorted")
+
+    def __init__(self, ctx, n=1 << 28, mode="keys", dtype="f32", dist="interleaved", split=0.5, descending=False,
+                 right=False, na=None, nb=None, **_):
+        if mode not in self.MODES:
+            raise ValueError(f"merge mode {mode!r}: one of {', '.join(self.MODES)}")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"merge dtype {dtype!r}: f32 or i32")
+        if dist not in ("interleaved", "disjoint", "equal"):
+            raise ValueError(f"merge dist {dist!r}: interleaved, disjoint or equal")
+        if na is None or nb is None:
+            if not 0.0 <= float(split) <= 1.0:
+                raise ValueError(f"merge split {split!r}: a fraction in [0, 1]")
+            na = int(round(int(n) * float(split)))
+            nb = int(n) - na
+        na, nb, dev = int(na), int(nb), ctx.device
+        super().__init__(ctx, {"n": na + nb, "na": na, "nb": nb, "mode": mode, "dtype": dtype, "dist": dist,
+                               "descending": bool(descending), "right": bool(right)}, "merge", "GB/s")
+        self.mode, self.descending, self.right = mode, bool(descending), bool(right)
+        self.search = mode.startswith("search")
+
+        def keys(count, seed, half):
+            """count random keys; half -1 / +1: from the lower / upper half of the range (dist disjoint), 0: all of it"""
+            if dtype == "f32":
+                lo, hi = (-1.0, 1.0) if half == 0 else ((-1.0, 0.0) if half < 0 else (0.0, 1.0))
+                x = ops.rand_uniform_(torch.empty(count, device=dev), seed, lo, hi)
+            else:
+                lo, hi = (-(1 << 31), 1 << 31) if half == 0 else ((-(1 << 31), 0) if half < 0 else (0, 1 << 31))
+                g = torch.Generator(device=dev).manual_seed(seed)
+                x = torch.randint(lo, hi, (count,), device=dev, generator=g, dtype=torch.int64).to(torch.int32)
+            if dist == "equal":
+                x.fill_(0.5 if dtype == "f32" else 1)
+            return x
+
+        def sorted_(x):
+            return torch.sort(x, descending=self.descending).values
+
+        first = -1 if dist == "disjoint" else 0
+        if self.descending:
+            first = -first
+        self.a = keys(na, 15000 + ctx.rank, first)
+        if mode != "search":
+            self.a = sorted_(self.a)
+        self.b = sorted_(keys(nb, 16000 + ctx.rank, -first))
+        self.va = torch.arange(na, device=dev, dtype=torch.int32) if mode == "pairs" else None
+        self.vb = torch.arange(na, na + nb, device=dev, dtype=torch.int32) if mode == "pairs" else None
+        self.out = None
+
+    def step(self):
+        if self.mode == "keys":
+            self.out = (ops.merge_keys(self.a, self.b, self.descending),)
+        elif self.mode == "pairs":
+            self.out = ops.merge_by_key(self.a, self.va, self.b, self.vb, self.descending)
+        elif self.mode == "index":
+            self.out = ops.merge(self.a, self.b, self.descending)
+        else:
+            self.out = (ops.searchsorted(self.b, self.a, self.right, self.descending, self.mode == "search_sorted"),)
+
+    def torch_step(self):
+        """The call a user makes today: a sort of the concatenation, or torch.searchsorted (ascending sequences only:
+        a descending one is searched through its flipped copy)."""
+        if self.search:
+            if not self.descending:
+                return torch.searchsorted(self.b, self.a, right=self.right)
+            return self.b.numel() - torch.searchsorted(self.b.flip(0), self.a, right=not self.right)
+        cat = torch.cat([self.a, self.b])
+        if self.mode == "keys":
+            return torch.sort(cat, descending=self.descending).values
+        if self.mode == "pairs":
+            r = torch.sort(cat, stable=True, descending=self.descending)
+            return r.values, torch.cat([self.va, self.vb])[r.indices]
+        return torch.sort(cat, stable=True, descending=self.descending)
+
+    def work_per_step(self):
+        # bytes moved: a merge reads every key once and writes it once, 4 more each way per value, 4 more for an index;
+        # the sorted search reads needles and haystack once and writes one int32 per needle; the general search is
+        # counted as its needles read and results written (what it reads of the haystack depends on the needles)
+        na, nb = self.a.numel(), self.b.numel()
+        if self.mode == "search":
+            return float(8 * na)
+        if self.mode == "search_sorted":
+            return float(4 * (na + nb) + 4 * na)
+        return float((na + nb) * {"keys": 8, "pairs": 16, "index": 12}[self.mode])
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gkeys_per_s"] = self.ctx.world * (self.a.numel() + self.b.numel()) * steps / seconds / 1e9
+        return rep
+
+    def check(self, reduce: bool = True):
+        """The outputs of the timed step against the torch oracle, exactly: the stable torch.sort of the concatenation
+        (keys bit for bit, indices, payload), or torch.searchsorted (the generated keys hold no NaN). Local only."""
+        if self.search:
+            ref = self.torch_step().int()
+            ok = self.out[0].dtype == torch.int32 and torch.equal(self.out[0], ref)
+        else:
+            ref = torch.sort(torch.cat([self.a, self.b]), stable=True, descending=self.descending)
+            ok = torch.equal(self.out[0].view(torch.int32), ref.values.view(torch.int32))
+            if self.mode != "keys":
+                ok = ok and self.out[1].dtype == torch.int32 and torch.equal(self.out[1], ref.indices.int())
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"elements_checked": self.a.numel() + (0 if self.search else self.b.numel()), "exact_vs_torch": ok,
+                "check_passed": ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
-             "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount}
+             "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
+             "merge": Merge}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

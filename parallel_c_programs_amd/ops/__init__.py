@@ -5,9 +5,9 @@ from .image import (SEED_3D, Camera, apply_region_mask, corner_seeds, create_vol
                     raycast, region2d, region2d_grow_padded_, region3d)
 from .sparse import CSR, SlicedCSR, banded_csr, create_vector, powerlaw_csr, spmv, spmv_banded
 from .stencil import init_grid, stencil5_reference, stencil5_step_, stencil5x2_step_, stencil5_fused_step_, stencil5_fused_spans_
-from .vector import (CMP_CODES, OP_CODES, argsort, axpy_, bincount, compact, compact_indices, compact_where, copy_, dot, fill_,
-                     gather_, histc, histogram, kth_value, rand_uniform_, reduce, reduce_by_key, run_length_encode, run_positions, scan,
-                     scan_by_key, scan_check, segmented_scan, select, select_indices, sort, sort_by_key, sort_keys, sum_by_key,
+from .vector import (CMP_CODES, OP_CODES, argsort, axpy_, bincount, bucketize, compact, compact_indices, compact_where, copy_, dot, fill_,
+                     gather_, histc, histogram, kth_value, merge, merge_by_key, merge_keys, rand_uniform_, reduce, reduce_by_key, run_length_encode, run_positions, scan,
+                     scan_by_key, scan_check, searchsorted, segmented_scan, select, select_indices, sort, sort_by_key, sort_keys, sum_by_key,
                      topk, unique, unique_consecutive, vadd, vmul)
 
 __all__ = [
@@ -23,4 +23,5 @@ __all__ = [
     "run_length_encode", "reduce_by_key", "unique_consecutive", "unique", "sum_by_key",
     "scan_by_key", "segmented_scan", "run_positions",
     "bincount", "histc", "histogram",
+    "merge_keys", "merge", "merge_by_key", "searchsorted", "bucketize",
 ]

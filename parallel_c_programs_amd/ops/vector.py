@@ -856,3 +856,155 @@ def histogram(x: torch.Tensor, edges: torch.Tensor, out: torch.Tensor | None = N
     v = v[(v >= edges[0]) & (v <= edges[nb])]
     b = (torch.searchsorted(edges.contiguous(), v, right=True) - 1).clamp(0, nb - 1)
     return _host_counts(b, nb, None, out, bool(accumulate))
+
+
+# ---------------------------------------------------------------- merge of sorted sequences / sorted search
+# For data that is ALREADY sorted: merge two sorted sequences in one pass, and find where values fall in a sorted
+# sequence (searchsorted / bucketize). float32 or int32 keys, flattened, in sort's order (above): float32 -0.0 == +0.0,
+# every NaN one key above +inf; descending reverses the order of the keys, not of ties. On the GPU the merge-path
+# diagonal partition (csrc/kernels/merge.hip; no counterpart in the reference programs): one thread per output tile of
+# MERGE_TILE keys finds where the tile starts in a and in b, one block per tile merges its two ranges through LDS. No
+# block waits for another, nothing can time out (scan_check() has nothing to report), nothing synchronises and the
+# outputs are the same on every call.
+#  * "Sorted" means non-decreasing in that order (non-increasing keys for descending=True). It is the caller's duty and
+#    is not checked: unsorted input gives an unspecified result, but nothing outside the tensors is touched.
+#  * DEFINITION of the merge: with cat = torch.cat([a.flatten(), b.flatten()]),
+#        merge(a, b, d)[1] == argsort(cat, descending=d)       and       merge(a, b, d)[0] == cat[indices], bit for bit.
+#    A tie goes to a: an element of a precedes an equal element of b. Unlike sort, nothing is transformed, so NaN
+#    payloads and the sign of zero come out as they went in.
+#  * searchsorted equals torch.searchsorted except for NaN: here a NaN value ties with the NaNs at the end of the
+#    sequence (right=False gives the index of the first NaN), where torch sends it to len(sequence) on both sides.
+#    Results are int32. values_sorted=True is the caller's promise that the values are sorted in the same order: with
+#    at least an eighth as many values as keys the search then runs as a merge of values and sequence that writes no
+#    keys (it reads both once, bandwidth-bound and load-balanced) instead of one two-level binary search per value
+#    (SEARCH_LDS_KEYS evenly spaced keys of the sequence in LDS, then the one interval left in global memory;
+#    latency-bound). Same result when the promise holds.
+#  * An input that is not contiguous is gathered first; a slice such as x[1:] is read where it lies.
+#  * Measured on one MI355X (profiles/r14_merge/README.md): merge_keys of 2^27 + 2^27 float32 keys 1.26 ms (0.93 when
+#    the sides do not interleave) against 8.14 ms for sort_keys(cat) and 9.5 for torch.sort(cat); merge_by_key 1.79 ms,
+#    merge 1.37 ms; 2.5-3.9x the time of a copy_ of the same bytes. searchsorted in 2^28 keys: 2^28 sorted values with
+#    values_sorted=True 2.18 ms against torch.searchsorted 7.40; 2^20 random values 0.27 against 0.32 ms. SLOWER than
+#    torch.searchsorted: 2^28 random values (72.2 against 69.5 ms) and sorted values that take the binary search, i.e.
+#    without the promise or fewer than an eighth of the keys (2^28: 8.2 against 7.4 ms; 2^20: 0.18 against 0.12 ms; the
+#    merge route would read the whole sequence for them: 0.86 ms).
+MERGE_TILE = 4352          # csrc/kernels/merge.hip kTile: output keys per block (256 lanes x 17 keys)
+SEARCH_LDS_KEYS = 8192     # csrc/kernels/merge.hip kSamples: a sequence up to here is searched in LDS alone
+MERGE_MAX_N = (1 << 31) - 1
+
+
+def _check_merge_keys(a: torch.Tensor, b: torch.Tensor, name: str, na: str = "a", nb: str = "b") -> None:
+    if a.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name}: {na} must be float32 or int32, got {a.dtype}")
+    if b.dtype != a.dtype:
+        raise TypeError(f"{name}: {nb} is {b.dtype}, {na} is {a.dtype}")
+    if b.device != a.device:
+        raise ValueError(f"{name}: {nb} is on {b.device}, {na} on {a.device}")
+
+
+def _check_merge(a: torch.Tensor, b: torch.Tensor, name: str) -> None:
+    _check_merge_keys(a, b, name)
+    if a.numel() + b.numel() > MERGE_MAX_N:
+        raise ValueError(f"{name}: {a.numel()} + {b.numel()} elements; indices are int32 (at most 2^31 - 1 together)")
+
+
+def _order_key64(x: torch.Tensor, descending: bool) -> torch.Tensor:
+    """int64 keys of flat x whose ascending order is the wanted order: radix_key.h's to_key, computed with torch."""
+    b = x.reshape(-1).contiguous().view(torch.int32).long() & 0xFFFFFFFF
+    if x.dtype == torch.float32:
+        mag = b & 0x7FFFFFFF
+        k = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b | 0x80000000)
+        k = torch.where(mag == 0, torch.full_like(k, 0x80000000), k)
+        k = torch.where(mag > 0x7F800000, torch.full_like(k, 0xFFFFFFFF), k)
+    else:
+        k = b ^ 0x80000000
+    return 0xFFFFFFFF - k if descending else k
+
+
+def _host_merge(a: torch.Tensor, b: torch.Tensor, descending: bool):
+    """(int32 view of the concatenation, int64 order of its stable sort)"""
+    cat = torch.cat([a.reshape(-1), b.reshape(-1)])
+    return cat.view(torch.int32), _host_order(cat, descending, 32)
+
+
+def merge_keys(a: torch.Tensor, b: torch.Tensor, descending: bool = False) -> torch.Tensor:
+    """The keys of two sorted tensors (float32 or int32, same dtype and device, either may be empty) merged into one
+    sorted 1-D tensor: sort_keys(cat(a, b)) for sorted inputs, with every key's bits kept (rules above)."""
+    _check_merge(a, b, "merge_keys")
+    if a.is_cuda:
+        return ops().merge_keys(a, b, bool(descending), None)
+    bits, order = _host_merge(a, b, bool(descending))
+    return bits[order].view(a.dtype)
+
+
+def merge(a: torch.Tensor, b: torch.Tensor, descending: bool = False):
+    """(keys, indices) of the merge of two sorted tensors: indices are int32 positions in cat(a.flatten(), b.flatten())
+    (i for a[i], a.numel() + i for b[i]) and equal argsort(cat, descending); keys == cat[indices] bit for bit. A tie
+    goes to a."""
+    _check_merge(a, b, "merge")
+    if a.is_cuda:
+        return tuple(ops().merge_index(a, b, bool(descending), True, None, None))
+    bits, order = _host_merge(a, b, bool(descending))
+    return bits[order].view(a.dtype), order.int()
+
+
+def merge_by_key(keys_a: torch.Tensor, values_a: torch.Tensor, keys_b: torch.Tensor, values_b: torch.Tensor,
+                 descending: bool = False):
+    """(keys, values): the merge of two sorted key tensors with their values (float32 or int32, the same dtype on both
+    sides, one per key, moved as bits) carried along. A tie goes to a."""
+    _check_merge_keys(keys_a, keys_b, "merge_by_key", "keys_a", "keys_b")
+    if values_a.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"merge_by_key: values must be float32 or int32, got {values_a.dtype}")
+    if values_b.dtype != values_a.dtype:
+        raise TypeError(f"merge_by_key: values_b is {values_b.dtype}, values_a is {values_a.dtype}")
+    for k, v, side in ((keys_a, values_a, "a"), (keys_b, values_b, "b")):
+        if v.numel() != k.numel():
+            raise ValueError(f"merge_by_key: {v.numel()} values for {k.numel()} keys on side {side}")
+        if v.device != keys_a.device:
+            raise ValueError(f"merge_by_key: values_{side} are on {v.device}, the keys on {keys_a.device}")
+    _check_merge(keys_a, keys_b, "merge_by_key")
+    if keys_a.is_cuda:
+        return tuple(ops().merge_pairs(keys_a, values_a, keys_b, values_b, bool(descending), None, None))
+    bits, order = _host_merge(keys_a, keys_b, bool(descending))
+    # (indexing an int32 view: a float gather would be free to quieten a signalling NaN payload)
+    vbits = torch.cat([values_a.reshape(-1), values_b.reshape(-1)]).view(torch.int32)[order]
+    return bits[order].view(keys_a.dtype), vbits.view(values_a.dtype)
+
+
+def searchsorted(sorted_sequence: torch.Tensor, values: torch.Tensor, right: bool = False, descending: bool = False,
+                 values_sorted: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """int32 tensor in the shape of values: for each value the number of keys of the flattened sorted_sequence that
+    precede it (right=False: the first position where it could be inserted) or that precede or equal it (right=True:
+    the last such position), in sort's order; descending=True for a sequence sorted descending. float32 or int32, both
+    tensors the same dtype and device, fewer than 2^31 elements each. Equal to torch.searchsorted EXCEPT for NaN: a NaN
+    value ties with the NaNs at the end of the sequence (with one trailing NaN in 7 keys, right=False gives 6 where
+    torch gives 7), and -0.0 ties with +0.0 as in torch. values_sorted=True promises that the values are sorted in the
+    same order and picks the merge route (rules above); the result is the same. out (optional): int32, values' shape
+    and device, overwritten. Sortedness is not checked. Does not synchronise."""
+    _check_merge_keys(sorted_sequence, values, "searchsorted", "sorted_sequence", "values")
+    if sorted_sequence.numel() > MERGE_MAX_N or values.numel() > MERGE_MAX_N:
+        raise ValueError(f"searchsorted: {sorted_sequence.numel()} keys and {values.numel()} values; results are int32 "
+                         "(at most 2^31 - 1 each)")
+    if out is not None:
+        if out.dtype != torch.int32:
+            raise TypeError(f"searchsorted: out must be int32, got {out.dtype}")
+        if out.device != values.device:
+            raise ValueError(f"searchsorted: out is on {out.device}, values on {values.device}")
+        if out.shape != values.shape:
+            raise ValueError(f"searchsorted: out must have shape {tuple(values.shape)}, got {tuple(out.shape)}")
+    if values.is_cuda:
+        direct = out is None or out.is_contiguous()
+        r = ops().searchsorted(sorted_sequence, values, bool(right), bool(descending), bool(values_sorted),
+                               out if direct else None)
+    else:
+        r = torch.searchsorted(_order_key64(sorted_sequence, bool(descending)), _order_key64(values, bool(descending)),
+                               right=bool(right)).int().reshape(values.shape)
+        direct = out is None
+    if direct:
+        return r
+    out.copy_(r)
+    return out
+
+
+def bucketize(values: torch.Tensor, boundaries: torch.Tensor, right: bool = False) -> torch.Tensor:
+    """torch.bucketize with int32 results: searchsorted(boundaries, values, right) for ascending boundaries."""
+    return searchsorted(boundaries, values, right=right)
