@@ -560,10 +560,14 @@ bool tile_aligned(int M, int N, int K) {
     return M > 0 && N > 0 && K > 0 && M % C::BM == 0 && N % C::BN == 0 && K % C::BK == 0;
 }
 
+// A leading dimension shorter than its row makes rows alias; variant 16 also sizes its A buffer resource by lda,
+// so lda == 0 (an expanded row) would read zeros. Every launcher refuses it.
+inline bool rows_fit(int N, int K, int lda, int ldb, int ldc) { return lda >= K && ldb >= N && ldc >= N; }
+
 template <class C>
 int launch_dma(const float* A, const float* B, float* Cm, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
                float beta, hipStream_t s) {
-    if (!tile_aligned<C>(M, N, K)) return PCMX_ERR_ARG;
+    if (!tile_aligned<C>(M, N, K) || !rows_fit(N, K, lda, ldb, ldc)) return PCMX_ERR_ARG;
     if ((lda | ldb) & 3 || (((uintptr_t)A | (uintptr_t)B) & 15)) return PCMX_ERR_ARG;
     const int grid = (M / C::BM) * (N / C::BN);
     if (beta != 0.f)
@@ -576,7 +580,7 @@ int launch_dma(const float* A, const float* B, float* Cm, int M, int N, int K, i
 int launch_rs(const float* A, const float* B, float* Cm, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
               float beta, hipStream_t s) {
     using C = CfgRS8;
-    if (!tile_aligned<C>(M, N, K)) return PCMX_ERR_ARG;
+    if (!tile_aligned<C>(M, N, K) || !rows_fit(N, K, lda, ldb, ldc)) return PCMX_ERR_ARG;
     if ((lda | ldb | ldc) & 3 || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)Cm) & 15)) return PCMX_ERR_ARG;
     // 32-bit buffer offsets: the block's A rows and the whole B panel must stay below 2 GiB
     if ((long long)C::BM * lda * 4 >= (1LL << 31) || (long long)K * ldb * 4 >= (1LL << 31)) return PCMX_ERR_ARG;
@@ -591,6 +595,7 @@ int launch_rs(const float* A, const float* B, float* Cm, int M, int N, int K, in
 int launch_direct(const float* A, const float* B, float* Cm, int M, int N, int K, int lda, int ldb, int ldc, float alpha,
                   float beta, int max_blocks, hipStream_t s) {
     if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 64) return PCMX_ERR_ARG;
+    if (!rows_fit(N, K, lda, ldb, ldc)) return PCMX_ERR_ARG;
     if ((lda | ldb | ldc) & 3 || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)Cm) & 15)) return PCMX_ERR_ARG;
     // every scalar byte offset (A row base + k, B k-row + column, C row + column) must stay below 2^31
     if ((long long)M * lda * 4 >= (1LL << 31) || (long long)K * ldb * 4 >= (1LL << 31) ||

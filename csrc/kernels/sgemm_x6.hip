@@ -6,8 +6,9 @@
 // v_mfma_f32_32x32x16_bf16 runs at 1024 FLOP/clk/SIMD (2.5 PF): 16x the rate for 8-bit significands.
 //  * Every fp32 operand x is split on the fly, in registers, into three bf16 values x = x0 + x1 + x2 EXACTLY
 //    (round-to-nearest split: x0 = bf16(x), x1 = bf16(x - x0), x2 = x - x0 - x1, which has <= 8 significant bits
-//    and so is a bf16; the two subtractions are exact). Holds for finite |x| >= 2^-110 (residuals stay normal);
-//    Inf/NaN operands produce NaN.
+//    and so is a bf16; the two subtractions are exact). Holds for 2^-110 <= |x| <= 0x7f7f7fff (3.3961e38): below,
+//    residuals leave the normal range; above, bf16 round-to-nearest sends x0 to infinity, so the finite operands
+//    0x7f7f8000 .. 0x7f7fffff give NaN where the f32 kernel is finite. Inf/NaN operands produce NaN.
 //  * a*b = sum over the 9 piece products; the 6 with i + j <= 2 are computed (a0b0, a0b1, a1b0, a0b2, a1b1,
 //    a2b0), the dropped three are below 2^-24 |a||b| (RNE pieces: |x1| <= 2^-8 |x|, |x2| <= 2^-16 |x|), i.e.
 //    below the rounding of one fp32 product. Each bf16 x bf16 product is exact in the f32 accumulator and the
@@ -229,6 +230,7 @@ namespace {
 template <class F>
 int launch_x6(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, F&& go) {
     if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 32) return PCMX_ERR_ARG;
+    if (lda < K || ldb < N || ldc < N) return PCMX_ERR_ARG;  // rows must not alias (as every sgemm.hip launcher)
     if ((lda | ldb | ldc) & 3 || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15)) return PCMX_ERR_ARG;
     if ((long long)M * lda * 4 >= (1LL << 31) || (long long)K * ldb * 4 >= (1LL << 31) ||
         (long long)M * ldc * 4 >= (1LL << 31))

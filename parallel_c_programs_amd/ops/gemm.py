@@ -16,8 +16,25 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+def _kernel_operand(x: torch.Tensor) -> torch.Tensor:
+    """`x` as the kernels take it: unit column stride, rows a multiple of 4 floats and at least a row apart, base
+    16-B aligned. Anything else (a transpose, a column slice, an expanded row, a misaligned view) is copied."""
+    def ok(t):
+        return t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0
+    if ok(x):
+        return x
+    x = x.contiguous()  # returns x itself when x is already contiguous (a misaligned view, a 1-row expand)
+    if x.data_ptr() % 16 or x.stride(0) < x.shape[1]:
+        x = x.clone(memory_format=torch.contiguous_format)
+    return x  # a row length that is no multiple of 4 is left to the caller's padding
+
+
 def sgemm(a: torch.Tensor, b: torch.Tensor, variant: int = -1) -> torch.Tensor:
-    """C = A @ B in fp32 (exact f32 products/sums via v_mfma_f32_32x32x2_f32 on gfx950)."""
+    """C = A @ B in fp32 (exact f32 products/sums via v_mfma_f32_32x32x2_f32 on gfx950).
+
+    `variant=20` computes the same product on the bf16 matrix cores by an exact 3-way operand split: fp32 accuracy
+    for operands with 2^-110 <= |x| <= 0x7f7f7fff (3.3961e38). Larger finite floats round to infinity in bf16 and give
+    NaN there, where the default kernel stays finite."""
     if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[0]:
         raise ValueError(f"sgemm: incompatible shapes {tuple(a.shape)} x {tuple(b.shape)}")
     if a.dtype != torch.float32 or b.dtype != torch.float32:
@@ -34,8 +51,7 @@ def sgemm(a: torch.Tensor, b: torch.Tensor, variant: int = -1) -> torch.Tensor:
     big = variant in (0, 16, 17, 18, 20) or (variant < 0 and -(-m // 256) * -(-n // 256) >= 192)
     tile, kq = (256, 64 if variant in (-1, 17, 18) else 32) if big else (128, 32)  # variant 20: K % 32
     mp, np_, kp = _round_up(m, tile), _round_up(n, tile), _round_up(k, kq)
-    ac = a if a.stride(1) == 1 and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0 else a.contiguous()
-    bc = b if b.stride(1) == 1 and b.stride(0) % 4 == 0 and b.data_ptr() % 16 == 0 else b.contiguous()
+    ac, bc = _kernel_operand(a), _kernel_operand(b)
     if (mp, np_, kp) == (m, n, k):
         return ops().sgemm(ac, bc, variant)
     ap = F.pad(ac, (0, kp - k, 0, mp - m))
