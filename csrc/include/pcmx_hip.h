@@ -365,12 +365,24 @@ int pcmx_stencil5x2_bf16(const void* u, void* out, int rows, int cols, int ld, i
                          long long global_row0, long long global_rows, float k, hipStream_t s);
 
 /* ---------------------------------------------------------------- SpMV */
+/* CSR-adaptive analysis: cuts the rows of a HOST row_ptr (n_rows + 1 entries) into work items of at most 1024
+ * nonzeros (4 x int64 words each, written to items_host); returns the item count, or -1 when max_items is too small
+ * (items_host == NULL: count only). */
 long long pcmx_spmv_csr_plan(const long long* row_ptr_host, int n_rows, void* items_host, long long max_items);
 /* the same cut with items of at most item_nnz (64..1024, multiple of 64) nonzeros */
 long long pcmx_spmv_csr_plan_nnz(const long long* row_ptr_host, int n_rows, void* items_host, long long max_items,
                                  int item_nnz);
+/* y = A x for a CSR matrix of any sparsity, one wave per item of pcmx_spmv_csr_plan (device arrays). */
 int pcmx_spmv_csr(const long long* row_ptr, const int* col, const float* val, const float* x, float* y, int n_rows,
                   const void* items, long long n_items, hipStream_t s);
+
+#define PCMX_SPMV_MAX_SLICES 32
+/* which part of a sliced product one pcmx_spmv_sliced call runs */
+enum {
+    PCMX_SPMV_ALL = 0,      /* products, combine and fix-up */
+    PCMX_SPMV_PRODUCTS = 1, /* the compact partials (ypart, extra) only */
+    PCMX_SPMV_COMBINE = 2   /* combine + fix-up of the partials a PCMX_SPMV_PRODUCTS call wrote */
+};
 /* XCD-sliced CSR (ops/sparse.py SlicedCSR): n_slices = 8 * phases <= PCMX_SPMV_MAX_SLICES; per nonzero col, val
  * and lrow (u16 offset of its row inside its item, rows counted among the rows the slice touches); per slice
  * nnz-balanced items over the slice's touched rows (a later piece of a split long row has row1 == row0).
@@ -379,36 +391,48 @@ int pcmx_spmv_csr(const long long* row_ptr, const int* col, const float* val, co
  * slice s touches row r; chunk_base[c * n_slices + s]: touched rows of slice s before row 64c) and a fix-up adds
  * extra[fix[k].item] to y[fix[k].row]. slice_nz0 / slice_item0 / slice_out0 are HOST arrays (n_slices,
  * n_slices + 1 and n_slices + 1 entries).
- * mode: bit 1 = items planned with item_nnz 512 (else 1024); bit 0 = skip the x gathers (lab measurement
- * only); mode >> 8 (if nonzero) = resident
- * blocks per CU (default 2). */
-#define PCMX_SPMV_MAX_SLICES 32
+ *  slice_colbase  HOST array of n_slices first tail columns: col holds the packed words (column offset | head flag |
+ *                 row offset << 22) and lrow is not read; NULL: the unpacked col + lrow arrays.
+ *  item_nnz       the size the items were planned with: 1024 or 512; 384 or 256 with slice_colbase only.
+ *  stage          PCMX_SPMV_ALL, PCMX_SPMV_PRODUCTS or PCMX_SPMV_COMBINE.
+ *  ballot_combine 1: the ballot-rank combine instead of the byte-packed scan (same bits; taken anyway when the
+ *                 partials reach 2^30, which the scan's 32-bit offsets cannot address); 0: the scan.
+ *  blocks_per_cu  resident product blocks per CU, 1..255; 0: the library default, 3.
+ *  phase_lo, phase_n  the products cover slices [8 phase_lo, 8 (phase_lo + phase_n)); phase_n 0: all from phase_lo.
+ * A value outside these sets returns PCMX_ERR_ARG before anything is launched. */
 int pcmx_spmv_sliced(const unsigned short* lrow, const int* col, const float* val, const float* x, float* ypart,
                      float* extra, float* y, int n_rows, int n_cols, int n_slices, const long long* slice_nz0,
                      const long long* slice_item0, const long long* slice_out0, const void* items,
-                     const unsigned* row_mask, const int* chunk_base, const void* fix, int n_fix, int mode,
+                     const unsigned* row_mask, const int* chunk_base, const void* fix, int n_fix, int item_nnz,
+                     int stage, int ballot_combine, int blocks_per_cu, int phase_lo, int phase_n,
                      const int* slice_colbase, hipStream_t s);
+/* products only of phases [a_lo, a_lo + a_n) of sliced matrix A and [b_lo, b_lo + b_n) of B (same x) in ONE launch.
+ * Packed layout only; item_nnz (256, 384, 512 or 1024) is the item size of both matrices, blocks_per_cu as above;
+ * nz0 / item0 / out0 / colbase: host arrays per matrix. Each matrix then combines its own partials. */
+int pcmx_spmv_sliced_pair(const float* x, int n_cols, int item_nnz, int blocks_per_cu, const int* col_a,
+                          const float* val_a, const void* items_a, float* ypart_a, float* extra_a, int s_a,
+                          const long long* nz0_a, const long long* item0_a, const long long* out0_a,
+                          const int* colbase_a, int a_lo, int a_n, const int* col_b, const float* val_b,
+                          const void* items_b, float* ypart_b, float* extra_b, int s_b, const long long* nz0_b,
+                          const long long* item0_b, const long long* out0_b, const int* colbase_b, int b_lo, int b_n,
+                          hipStream_t s);
 /* the combine + split-row fix-up (+ send-buffer pack: sendbuf[send_slot[p]] = y[r] for p in send_ptr[r] ..
- * send_ptr[r + 1]) of the partials a products-only pcmx_spmv_sliced call (mode bit 4) wrote, in ONE launch.
- * slice_out0: host array of n_slices + 1 partial offsets; fix: int2 {item, row} sorted by row; fix_chunk0: the fix range
- * of every 64-row chunk (n_rows / 64 + 2 ints, or NULL: no split rows); send_ptr (n_rows + 1) / send_slot / sendbuf
- * may be NULL (no pack). Same bits as combine + fix-up. */
-/* products only of phases [a_lo, a_lo + a_n) of sliced matrix A and [b_lo, b_lo + b_n) of B (same x) in ONE launch
- * (production packed layout; item_mode 2: 512-nnz items); nz0 / item0 / out0 / colbase: host arrays per matrix */
-int pcmx_spmv_sliced_pair(const float* x, int n_cols, int item_mode, int mode, const int* col_a, const float* val_a,
-                          const void* items_a, float* ypart_a, float* extra_a, int s_a, const long long* nz0_a,
-                          const long long* item0_a, const long long* out0_a, const int* colbase_a, int a_lo, int a_n,
-                          const int* col_b, const float* val_b, const void* items_b, float* ypart_b, float* extra_b,
-                          int s_b, const long long* nz0_b, const long long* item0_b, const long long* out0_b,
-                          const int* colbase_b, int b_lo, int b_n, hipStream_t s);
+ * send_ptr[r + 1]) of the partials a products-only call (PCMX_SPMV_PRODUCTS, or pcmx_spmv_sliced_pair) wrote, in ONE
+ * launch. slice_out0: host array of n_slices + 1 partial offsets (fewer than 2^30 partials); fix: int2 {item, row}
+ * sorted by row; fix_chunk0: the fix range of every 64-row chunk (n_rows / 64 + 2 ints, or NULL: no split rows);
+ * send_ptr (n_rows + 1) / send_slot / sendbuf may be NULL (no pack). Same bits as combine + fix-up. */
 int pcmx_spmv_sliced_combine(const float* ypart, const unsigned* row_mask, const int* chunk_base,
                              const long long* slice_out0, int n_slices, float* y, int n_rows, const float* extra,
                              const void* fix, const int* fix_chunk0, const int* send_ptr, const int* send_slot,
                              float* sendbuf, hipStream_t s);
+/* banded product with implicit column indices (bands a .. e as in the reference's create_csr_matrix): variant 8 of
+ * pcmx_spmv_banded_variant */
 int pcmx_spmv_banded(const float* vals, const long long* row_off, int n, int a, int b, int c, int d, int e,
                      const float* x, float* y, hipStream_t s);
-/* variant 0: one wave per row (strided band loops, global x); 1: LDS-staged x windows, row blocks, 4-B loads;
- * 2 / 3: the same with 16-B value loads, 2 / 4 rows per wave in flight */
+/* variant 0: one wave per row (strided band loops, global x); 1: LDS-staged x windows, 16 rows per block, 2 rows per
+ * wave in flight, 4-B value loads; 8: each 16-row block's values as one aligned 16-B stream (falls back to 1 for rows
+ * under 256 nonzeros, values not 16-B aligned, a stream capture before the geometry's table exists, or a failed table
+ * allocation). 1 and 8 fall back to 0 for rows above 16 x 64 nonzeros. Any other variant: PCMX_ERR_ARG. */
 int pcmx_spmv_banded_variant(const float* vals, const long long* row_off, int n, int a, int b, int c, int d, int e,
                              const float* x, float* y, int variant, hipStream_t s);
 

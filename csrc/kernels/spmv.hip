@@ -45,6 +45,7 @@ constexpr int kRpPerLane = (kItemRows + 1 + 63) / 64;  // row pointers per lane 
 constexpr int kPerLane = kItemNnz / kWave;  // nonzeros per lane
 constexpr int kMaxSlices = PCMX_SPMV_MAX_SLICES;
 constexpr int kPersistBlocks = 3;  // sliced kernel: resident blocks (of 4 waves) per CU (161 VGPRs -> 3 waves/SIMD)
+constexpr int kBandedRows = 16;    // banded kernels: rows per block
 
 // ------------------------------------------------------------------------------------------ plain CSR
 // One wave per item. All column/value loads of the item AND its row pointers are issued up front, then all
@@ -117,9 +118,9 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmv_csr_items_kernel(
 // ------------------------------------------------------------------------------------------ XCD-sliced CSR
 // Layout per slice: col/val of its nonzeros (slice-major, row order kept), lrow = the u16 row offset of each
 // nonzero inside its item, and nnz-balanced items (a later piece of a split long row has row1 == row0).
-// A slice averages ~1 nonzero per row, so rows are not reduced from row pointers: the wave scatters its
-// products with LDS float adds (ds_add_f32) into the item's rows. One wave owns its LDS rows and its adds
-// execute in program/lane order, so the sums are reproducible run to run.
+// A slice averages ~1 nonzero per row, so rows are not reduced from row pointers: an item's nonzeros are sorted
+// by row and the wave sums each row with a segmented scan over its lanes (sliced_step), in a fixed order, so the
+// sums are reproducible run to run. (An LDS-scatter form of the row sums lost to it in round 2, profiles/r2_spmv.)
 //
 // Persistent waves with a one-item software pipeline: a wave issues item k's gathers as soon as its columns
 // are in registers, then item k+1's stream loads, and only then waits for the gathers, so the next item's
@@ -147,7 +148,7 @@ struct SliceMeta {
     unsigned char part[kMaxSlices];  // 1: slice s belongs to the paired matrix `b`
     SlicePart b;
 };
-// Packed layout (kMode bit 3): ONE 32-bit word per nonzero instead of a 4-B column + a 2-B row offset —
+// Packed layout (kPacked): ONE 32-bit word per nonzero instead of a 4-B column + a 2-B row offset —
 //   bits 0-20 column - colbase[s] (tail) or the column itself (head, bit 21 set), bits 22-31 the row offset in
 //   the item (< 1023) — 6 -> 4 B of index stream per nonzero and one stream load instruction fewer per element.
 constexpr unsigned kPackColMask = 0x1FFFFFu, kPackHead = 0x200000u;
@@ -164,7 +165,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned b
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
 }
 
-template <int kPL, bool kPacked = false>
+template <int kPL, bool kPacked>
 __device__ __forceinline__ void load_item_stream(const int* __restrict__ col, const float* __restrict__ val,
                                                  const unsigned short* __restrict__ lrow, const Item& it,
                                                  StreamRegs<kPL>& q, int lane) {
@@ -190,15 +191,11 @@ struct SlicedCtx {
     const Item* items;
     float* yp;
     float* extra;
-    float* yw;
     long long i1, stride;
     int lane;
     int colbase;  // packed layout: first tail column of the slice
 };
 
-// One pipeline step: gathers of the current item, stream loads of the next item, then the current item's
-// LDS scatter and stores. Called alternately with the two register sets swapped (a register copy would make
-// the compiler wait for the prefetch).
 // One step of a segmented inclusive scan over the wave (Hillis-Steele on DPP): (v, f) = (running sum, "a segment
 // starts at or after the combined range"); a lane without a source in this pattern keeps its value (old = 0).
 template <int kCtrl, int kRowMask>
@@ -220,25 +217,25 @@ __device__ __forceinline__ void seg_scan_wave(float& v, int& f) {
 // One pipeline step: gathers of the current item, stream loads of the next item, then the current item's row
 // sums and stores. Called alternately with the two register sets swapped (a register copy would make the
 // compiler wait for the prefetch).
-// kMode bit 2 (production): row sums by a segmented DPP scan per 64-element stripe — an item's nonzeros are
-// sorted by row, so element i = j * 64 + lane continues the row of element i - 1 unless its lrow differs; the
-// lane holding a row's LAST element stores the row sum straight to the compact partials (a row running past a
-// stripe carries its partial sum into the next stripe). No LDS, no barriers. Otherwise: LDS scatter (ds_add_f32
-// into the item's rows, then one store per row) — measured LDS-issue bound (34% of wave cycles in
-// SQ_WAIT_INST_LDS, profiles/r2_spmv).
-template <int kMode, int kPL, bool kTS = false>
+// Row sums by a segmented DPP scan per 64-element stripe — an item's nonzeros are sorted by row, so element
+// i = j * 64 + lane continues the row of element i - 1 unless its lrow differs; the lane holding a row's LAST
+// element stores the row sum straight to the compact partials (a row running past a stripe carries its partial
+// sum into the next stripe). No LDS, no barriers.
+// Partial stores: temporal on the packed layout (the ~340 MB of compact partials are re-read by the combine right
+// after the product, and non-temporal stores evicted them early: 0.633-0.652 -> 0.628 ms per step at 1e8 nnz,
+// bit-identical; profiles/r4_spmv/store_temporal_partials.txt), non-temporal on the unpacked one. The policy follows
+// the layout because that round-4 A/B was run on the packed layout only; the unpacked kernels keep the stores they had.
+template <bool kPacked, int kPL>
 __device__ __forceinline__ bool sliced_step(const SlicedCtx& k, long long& it, const Item& cur, const StreamRegs<kPL>& q,
                                             Item& nitem, StreamRegs<kPL>& nq) {
-    constexpr int kStAux = kTS ? 0 : 2;  // partial stores: temporal (kTS: may stay in L2 / MALL for the combine) or nt
-    constexpr bool kPacked = (kMode & 8) != 0;
+    constexpr int kStAux = kPacked ? 0 : 2;  // 0: temporal (may stay in L2 / MALL for the combine), 2: nt
     const int lane = k.lane;
     float g[kPL];
 #pragma unroll
     for (int j = 0; j < kPL; ++j) {
         const unsigned w = (unsigned)q.c[j];
         const unsigned c = kPacked ? (w & kPackColMask) + ((w & kPackHead) ? 0u : (unsigned)k.colbase) : w;
-        g[j] = (kMode & 1) ? __int_as_float(q.c[j])
-                           : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(k.rx, c * 4, 0, 0));
+        g[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(k.rx, c * 4, 0, 0));
     }
     // the row offset of element j (packed: the word's top bits; read before nq may reuse q's registers)
     auto lrow_of = [&](int j) __attribute__((always_inline)) {
@@ -250,77 +247,38 @@ __device__ __forceinline__ bool sliced_step(const SlicedCtx& k, long long& it, c
     load_item_stream<kPL, kPacked>(k.col, k.val, k.lrow, nitem, nq, lane);  // (a harmless re-read of the last item)
     const int n = (int)(cur.nz1 - cur.nz0);
     const int nrows = cur.row1 - cur.row0;
-    if constexpr ((kMode & 4) != 0) {
-        if (nrows <= 1) {  // whole short row or a piece of a long row (later piece: row1 == row0 -> extra[it])
-            float acc = 0.f;
+    if (nrows <= 1) {  // whole short row or a piece of a long row (later piece: row1 == row0 -> extra[it])
+        float acc = 0.f;
 #pragma unroll
-            for (int j = 0; j < kPL; ++j) acc += q.v[j] * g[j];
-            acc = pcmx::wave_reduce<float, 0>(acc);
-            const auto r1 = rsrc(nrows == 1 ? k.yp + cur.row0 : k.extra + it, 4u);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc), r1, lane == 0 ? 0u : 0x80000000u, 0, kStAux);
-        } else {
-            const auto ry = rsrc(k.yp + cur.row0, (unsigned)nrows * 4);
-            float carry = 0.f;
-            int rprev = -1;  // row of the element before this stripe (wave-uniform)
-#pragma unroll
-            for (int j = 0; j < kPL; ++j) {
-                const bool valid = j * kWave + lane < n;
-                const int r = valid ? lrow_of(j) : 0x10000;  // past the item: one trailing non-row segment
-                float v = valid ? q.v[j] * g[j] : 0.f;
-                const int rp = __builtin_amdgcn_update_dpp(rprev, r, 0x138, 0xf, 0xf, false);  // wave_shr:1
-                int f = r != rp;
-                seg_scan_wave(v, f);
-                v = f ? v : v + carry;  // lanes still in the row carried in from the previous stripe
-                const int rnext0 = (j + 1 < kPL && (j + 1) * kWave < n)
-                                       ? __builtin_amdgcn_readlane(lrow_of(j + 1 < kPL ? j + 1 : j), 0)
-                                       : 0x10000;
-                const int rn = __builtin_amdgcn_update_dpp(rnext0, r, 0x130, 0xf, 0xf, false);  // wave_shl:1
-                const bool tail = valid && r != rn;
-                // predicated: only a row's last lane issues its store (an out-of-range offset on the other lanes
-                // still cost them address slots: 0.706 -> 0.693 ms per product, profiles/r2_spmv/store_ab.txt)
-                if (tail) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, (unsigned)r * 4u, 0, kStAux);
-                const int r63 = __builtin_amdgcn_readlane(r, 63);
-                carry = r63 == rnext0 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)) : 0.f;
-                rprev = r63;
-            }
-        }
+        for (int j = 0; j < kPL; ++j) acc += q.v[j] * g[j];
+        acc = pcmx::wave_reduce<float, 0>(acc);
+        const auto r1 = rsrc(nrows == 1 ? k.yp + cur.row0 : k.extra + it, 4u);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc), r1, lane == 0 ? 0u : 0x80000000u, 0, kStAux);
     } else {
-        float* dst;
-        int nstore;
-        if (nrows <= 1) {
-            float acc = 0.f;
-#pragma unroll
-            for (int j = 0; j < kPL; ++j) acc += q.v[j] * g[j];
-            acc = pcmx::wave_reduce<float, 0>(acc);
-            if (lane == 0) k.yw[0] = acc;
-            dst = nrows == 1 ? k.yp + cur.row0 : k.extra + it;
-            nstore = 1;
-        } else {
-#pragma unroll
-            for (int j = 0; j < kPL; ++j) {  // compact rows: every row of an item holds >= 1 of its <= 64 kPL nonzeros
-                const int i = j * kWave + lane;
-                if (i < nrows) k.yw[i] = 0.f;
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#pragma unroll
-            for (int j = 0; j < kPL; ++j) {
-                const int i = j * kWave + lane;
-                if (i < n) atomicAdd(&k.yw[lrow_of(j)], q.v[j] * g[j]);
-            }
-            dst = k.yp + cur.row0;
-            nstore = nrows;
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const auto ry = rsrc(dst, (unsigned)nstore * 4);
+        const auto ry = rsrc(k.yp + cur.row0, (unsigned)nrows * 4);
+        float carry = 0.f;
+        int rprev = -1;  // row of the element before this stripe (wave-uniform)
 #pragma unroll
         for (int j = 0; j < kPL; ++j) {
-            const int i = j * kWave + lane;
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(k.yw[i]), ry, i * 4, 0, 2);
+            const bool valid = j * kWave + lane < n;
+            const int r = valid ? lrow_of(j) : 0x10000;  // past the item: one trailing non-row segment
+            float v = valid ? q.v[j] * g[j] : 0.f;
+            const int rp = __builtin_amdgcn_update_dpp(rprev, r, 0x138, 0xf, 0xf, false);  // wave_shr:1
+            int f = r != rp;
+            seg_scan_wave(v, f);
+            v = f ? v : v + carry;  // lanes still in the row carried in from the previous stripe
+            const int rnext0 = (j + 1 < kPL && (j + 1) * kWave < n)
+                                   ? __builtin_amdgcn_readlane(lrow_of(j + 1 < kPL ? j + 1 : j), 0)
+                                   : 0x10000;
+            const int rn = __builtin_amdgcn_update_dpp(rnext0, r, 0x130, 0xf, 0xf, false);  // wave_shl:1
+            const bool tail = valid && r != rn;
+            // predicated: only a row's last lane issues its store (an out-of-range offset on the other lanes
+            // still cost them address slots: 0.706 -> 0.693 ms per product, profiles/r2_spmv/store_ab.txt)
+            if (tail) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, (unsigned)r * 4u, 0, kStAux);
+            const int r63 = __builtin_amdgcn_readlane(r, 63);
+            carry = r63 == rnext0 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)) : 0.f;
+            rprev = r63;
         }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // next item's zeroing after these LDS reads
     }
     it = nxt;
     return more;
@@ -328,12 +286,12 @@ __device__ __forceinline__ bool sliced_step(const SlicedCtx& k, long long& it, c
 
 // The item loop of one wave over slice s (items [it, i1), stride apart) of ONE matrix, its arrays as __restrict__
 // parameters (after inlining they keep their no-alias scopes).
-template <int kMode, int kPL, bool kTS>
+template <bool kPacked, int kPL>
 __device__ __forceinline__ void sliced_wave(const unsigned short* __restrict__ lrow, const int* __restrict__ col,
                                             const float* __restrict__ val, const float* __restrict__ x, int n_cols,
                                             float* __restrict__ ypart, float* __restrict__ extra,
                                             const Item* __restrict__ items, const SliceMeta& meta, int s, long long it,
-                                            long long i1, long long stride, float* yw) {
+                                            long long i1, long long stride) {
     SlicedCtx k;
     k.i1 = i1;
     k.stride = stride;
@@ -341,12 +299,12 @@ __device__ __forceinline__ void sliced_wave(const unsigned short* __restrict__ l
     k.col = col + base, k.val = val + base, k.lrow = lrow + base;
     k.colbase = meta.colbase[s];
     k.rx = rsrc(x, (unsigned)n_cols * 4);
-    k.items = items, k.extra = extra, k.yp = ypart + meta.out0[s], k.yw = yw;
+    k.items = items, k.extra = extra, k.yp = ypart + meta.out0[s];
     k.lane = pcmx::lane_id();
     Item ia = items[it], ib;
     StreamRegs<kPL> qa, qb;
-    load_item_stream<kPL, (kMode & 8) != 0>(k.col, k.val, k.lrow, ia, qa, k.lane);
-    while (sliced_step<kMode, kPL, kTS>(k, it, ia, qa, ib, qb) && sliced_step<kMode, kPL, kTS>(k, it, ib, qb, ia, qa)) {
+    load_item_stream<kPL, kPacked>(k.col, k.val, k.lrow, ia, qa, k.lane);
+    while (sliced_step<kPacked, kPL>(k, it, ia, qa, ib, qb) && sliced_step<kPacked, kPL>(k, it, ib, qb, ia, qa)) {
     }
 }
 
@@ -354,12 +312,11 @@ __device__ __forceinline__ void sliced_wave(const unsigned short* __restrict__ l
 // loop is instantiated once per matrix with that matrix's arrays as its own __restrict__ parameters: selecting the
 // pointers per slice in front of ONE loop cost the 1e8-nnz single-matrix product 8% (0.639 -> 0.691 ms in the round-5
 // A/B of scripts/spmv_step_time.py: ~400 more instructions in the item loop).
-template <int kMode, int kPL, bool kTS = false, bool kPaired = false>
+template <bool kPacked, int kPL, bool kPaired = false>
 __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmv_sliced_kernel(
     const unsigned short* __restrict__ lrow, const int* __restrict__ col, const float* __restrict__ val,
     const float* __restrict__ x, int n_cols, float* __restrict__ ypart, float* __restrict__ extra,
     const Item* __restrict__ items, SliceMeta meta, int blocks_per_slice, int phase_lo) {
-    __shared__ float yl[kWavesPerBlock][kItemRows + 1];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int b = blockIdx.x;
     const int phase = phase_lo + b / (8 * blocks_per_slice);
@@ -369,10 +326,10 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmv_sliced_kernel(
     const long long it = meta.item0[s] + (long long)((b >> 3) % blocks_per_slice) * kWavesPerBlock + w;
     if (it >= i1) return;
     if (kPaired && meta.part[s])  // (wave-uniform) a slice of the paired matrix
-        sliced_wave<kMode, kPL, kTS>(meta.b.lrow, meta.b.col, meta.b.val, x, n_cols, meta.b.ypart, meta.b.extra,
-                                     meta.b.items, meta, s, it, i1, stride, yl[w]);
+        sliced_wave<kPacked, kPL>(meta.b.lrow, meta.b.col, meta.b.val, x, n_cols, meta.b.ypart, meta.b.extra,
+                                  meta.b.items, meta, s, it, i1, stride);
     else
-        sliced_wave<kMode, kPL, kTS>(lrow, col, val, x, n_cols, ypart, extra, items, meta, s, it, i1, stride, yl[w]);
+        sliced_wave<kPacked, kPL>(lrow, col, val, x, n_cols, ypart, extra, items, meta, s, it, i1, stride);
 }
 
 // y[r] = sum over the slices touching row r (bit k of mask[r]) of that slice's compact partial, in slice order.
@@ -591,17 +548,19 @@ __device__ __forceinline__ void band_limits(int n, int a, int b, int c, int d, i
     for (int k = 0; k < 5; ++k) hi[k] = max(hi[k], lo[k]);
 }
 
-// Banded SpMV with implicit column indices (ref s_matrix `multiply`, spmv.c:212-329), one block per R rows.
+// Banded SpMV with implicit column indices (ref s_matrix `multiply`, spmv.c:212-329), one block per R = kBandedRows
+// rows; a wave keeps U of its rows in flight (2 in the LDS-window kernel, 1 for the clipped blocks of the stream kernel).
 //  * x: band k of rows r0..r0+R-1 reads the contiguous window [lo_k(r0), hi_k(r0+R-1)) — one row's band shifted
 //    by up to R-1 — so the block stages the 5 windows in LDS once (coalesced) and every nonzero reads x there.
 //  * values: row i's nonzeros are contiguous; a wave takes whole rows, lane j reads value j + 64m (coalesced
 //    256-B wave loads, all ceil(nnz/64) <= NL of a row issued before use, two rows in flight per wave).
 //  * no per-row metadata: the rows' nonzero counts and band limits are computed in registers (a wave prefix
 //    scan of the R counts gives each row's offset from the block's first row); row_off is read ONCE per block.
-template <int R, int NL, int U>
+template <int NL, int U>
 __device__ __forceinline__ void banded_rows_body(const float* __restrict__ vals, const long long* __restrict__ row_off,
                                                  int n, int a, int b, int c, int d, int e, const float* __restrict__ x,
                                                  float* __restrict__ y, float* xw, int r0) {
+    constexpr int R = kBandedRows;
     static_assert(R <= kWave && R % 4 == 0, "rows per block");
     const int lane = pcmx::lane_id();
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
@@ -689,16 +648,16 @@ __device__ __forceinline__ void banded_rows_body(const float* __restrict__ vals,
         }
     }
 }
-template <int R, int NL, int U = 2>
+template <int NL>
 __global__ __launch_bounds__(256) void spmv_banded_lds_kernel(const float* __restrict__ vals,
                                                               const long long* __restrict__ row_off, int n, int a, int b,
                                                               int c, int d, int e, const float* __restrict__ x,
                                                               float* __restrict__ y) {
     extern __shared__ float xw[];
-    banded_rows_body<R, NL, U>(vals, row_off, n, a, b, c, d, e, x, y, xw, (int)blockIdx.x * R);
+    banded_rows_body<NL, 2>(vals, row_off, n, a, b, c, d, e, x, y, xw, (int)blockIdx.x * kBandedRows);
 }
 
-// Variant 8 (block stream): a block of R rows reads its values — ONE contiguous CSR range — as one aligned 16-B
+// Variant 8 (block stream): a block of R = kBandedRows rows reads its values — ONE contiguous CSR range — as one aligned 16-B
 // stream through a buffer descriptor over exactly that range's float4s, instead of row by row with 4-B loads.
 // Valid for blocks of UNCLIPPED rows (every band inside [0, n)): all such rows hold L nonzeros in the same band
 // layout, and band k's window of a block starting at row r0 begins at column r0 + delta[k], so every block's five
@@ -722,10 +681,12 @@ struct BandGeo {
 // device memory per geometry, banded_lut_table) and each block copies it into LDS with kLutPer 16-B loads per thread
 // issued with the window loads (building it per block cost ~1/3 of the kernel's VALU work: profiles/r4_spmv).
 constexpr int kLutPer = 4;  // table entries per thread: 4 * ql <= 1024, checked by the launcher
-template <int R, int NV, int XW>
+constexpr int kStreamNV = 10;  // value float4s per lane: a wave's quarter of 16 rows of up to 1024 nonzeros
+constexpr int kStreamXW = 3;   // x-window floats per thread (256 * kStreamXW >= W + 3, checked by the launcher)
 __device__ __forceinline__ void banded_stream_block(const float* __restrict__ vals, long long off0, const BandGeo& g,
                                                     const pcmx::i32x4* __restrict__ lut_g, int rb_begin, int sb_idx,
                                                     const float* __restrict__ x, float* __restrict__ y, float* sm) {
+    constexpr int R = kBandedRows, NV = kStreamNV, XW = kStreamXW;
     const int L = g.L;
     // four copies of the x windows, copy q shifted by q (xq[q][i] = window[i + q]), each 16-B aligned: the four x
     // values of a float4 whose slots s .. s + 3 are consecutive are ONE aligned ds_read_b128 from copy s & 3
@@ -877,7 +838,6 @@ __device__ __forceinline__ void banded_stream_block(const float* __restrict__ va
 // Variant 8 launch: ONE grid; its first nclip blocks take the clipped first / last row blocks (row blocks [0, nfront)
 // and [back0, ...)) with variant 1's row body, the rest stream. Dispatched first, the few clipped blocks (whose cost
 // is latency: ~10 us as a launch of their own) overlap the streaming blocks instead of adding to them.
-template <int R, int NV, int XW>
 __global__ __launch_bounds__(256) void spmv_banded_stream_kernel(const float* __restrict__ vals,
                                                                  const long long* __restrict__ row_off, int n, int a,
                                                                  int b, int c, int d, int e, int nfront, int back0,
@@ -888,10 +848,10 @@ __global__ __launch_bounds__(256) void spmv_banded_stream_kernel(const float* __
     const int bid = (int)blockIdx.x;
     if (bid < nclip) {
         const int rb = bid < nfront ? bid : back0 + (bid - nfront);
-        banded_rows_body<R, 16, 1>(vals, row_off, n, a, b, c, d, e, x, y, sm, rb * R);
+        banded_rows_body<16, 1>(vals, row_off, n, a, b, c, d, e, x, y, sm, rb * kBandedRows);
         return;
     }
-    banded_stream_block<R, NV, XW>(vals, off0, g, lut_g, rb_begin, bid - nclip, x, y, sm);
+    banded_stream_block(vals, off0, g, lut_g, rb_begin, bid - nclip, x, y, sm);
 }
 
 // fallback for rows longer than 16 x 64 nonzeros: one wave per row, strided band loops
@@ -962,28 +922,32 @@ extern "C" int pcmx_spmv_csr(const long long* row_ptr, const int* col, const flo
     return (int)hipGetLastError();
 }
 
-// Partial stores of the sliced product are temporal (round 4: the ~340 MB of compact partials are re-read by the
-// combine right after the product, and non-temporal stores evicted them early: 0.633-0.652 -> 0.628 ms per step at
-// 1e8 nnz, bit-identical; scripts/spmv_store_lab.py, profiles/r4_spmv/store_temporal_partials.txt). mode bit 26 (lab,
-// an explicit per-call parameter): non-temporal partial stores instead.
-constexpr int kModeNtPartials = 1 << 26;
-// mode bit 27: items of 256 nonzeros (4 per lane; packed layout only) — the short launches of a distributed rank's
-// column-split step give each wave only a few items, so shorter items spread the same work over more of them
-constexpr int kMode256 = 1 << 27;
-// mode bit 28: items of 384 nonzeros (6 per lane; packed layout only), between the 256 and 512 of a distributed rank
-constexpr int kMode384 = 1 << 28;
+namespace {
+// Items of 1024 / 512 nonzeros (16 / 8 per lane) exist in both layouts; 384 / 256 (6 / 4 per lane) in the packed one
+// only — the short launches of a distributed rank's column-split step give each wave only a few items, so shorter
+// items spread the same work over more of them.
+bool sliced_item_ok(int item_nnz, bool packed) {
+    return item_nnz == 1024 || item_nnz == 512 || (packed && (item_nnz == 384 || item_nnz == 256));
+}
+bool sliced_blocks_ok(int blocks_per_cu) { return blocks_per_cu >= 0 && blocks_per_cu <= 255; }
+}  // namespace
 
 extern "C" int pcmx_spmv_sliced(const unsigned short* lrow, const int* col, const float* val, const float* x,
                                 float* ypart, float* extra, float* y, int n_rows, int n_cols, int n_slices,
                                 const long long* slice_nz0, const long long* slice_item0, const long long* slice_out0,
                                 const void* items, const unsigned* row_mask, const int* chunk_base, const void* fix,
-                                int n_fix, int mode, const int* slice_colbase, hipStream_t s) {
+                                int n_fix, int item_nnz, int stage, int ballot_combine, int blocks_per_cu, int phase_lo,
+                                int phase_n, const int* slice_colbase, hipStream_t s) {
+    if (!sliced_item_ok(item_nnz, slice_colbase != nullptr) || !sliced_blocks_ok(blocks_per_cu) ||
+        (stage != PCMX_SPMV_ALL && stage != PCMX_SPMV_PRODUCTS && stage != PCMX_SPMV_COMBINE) ||
+        (ballot_combine != 0 && ballot_combine != 1) || phase_lo < 0 || phase_n < 0)
+        return PCMX_ERR_ARG;
     if (n_rows <= 0) return 0;
     if (n_slices <= 0 || n_slices % 8 || n_slices > kMaxSlices) return (int)hipErrorInvalidValue;
-    const int persist_blocks = (mode >> 8) & 0xff ? (mode >> 8) & 0xff : kPersistBlocks;
-    // bits 16-20 / 21-25: the product launch covers phases [ph_lo, ph_lo + ph_n) (8 slices, one per XCD, per phase;
-    // ph_n = 0: all): a column-split caller multiplies the slices of the columns it already holds first
-    const int ph_all = n_slices / 8, ph_lo = (mode >> 16) & 31, ph_n = (mode >> 21) & 31 ? (mode >> 21) & 31 : ph_all - ph_lo;
+    const int persist_blocks = blocks_per_cu ? blocks_per_cu : kPersistBlocks;
+    // the product launch covers phases [ph_lo, ph_lo + ph_n) (8 slices, one per XCD, per phase): a column-split
+    // caller multiplies the slices of the columns it already holds first
+    const int ph_all = n_slices / 8, ph_lo = phase_lo, ph_n = phase_n ? phase_n : ph_all - ph_lo;
     if (ph_lo + ph_n > ph_all || ph_n <= 0) return (int)hipErrorInvalidValue;
     SliceMeta meta{};
     SliceOut so{};
@@ -1002,9 +966,9 @@ extern "C" int pcmx_spmv_sliced(const unsigned short* lrow, const int* col, cons
         meta.item1[k] = slice_item0[k + 1];
     }
     so.out0[n_slices] = slice_out0[n_slices];
-    // bit 4: products only (no combine / fix-up), bit 5: combine + fix-up only — a row-chunked caller runs chunk
-    // q's combine on a second stream while chunk q + 1's products run
-    if (most > 0 && !(mode & 32)) {
+    // PCMX_SPMV_PRODUCTS: no combine / fix-up, PCMX_SPMV_COMBINE: combine + fix-up only — a row-chunked caller runs
+    // chunk q's combine on a second stream while chunk q + 1's products run
+    if (most > 0 && stage != PCMX_SPMV_COMBINE) {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -1015,45 +979,32 @@ extern "C" int pcmx_spmv_sliced(const unsigned short* lrow, const int* col, cons
         const unsigned nb = (unsigned)(bp * 8 * ph_n);
         const Item* it = reinterpret_cast<const Item*>(items);
         const dim3 blk(kWavesPerBlock * kWave);
-        // bit 0: skip the x gathers (lab), bit 1: items of 512 nonzeros (8 per lane), bit 2: LDS row sums (lab)
-#define PCMX_SLICED(M, PL) spmv_sliced_kernel<M, PL><<<nb, blk, 0, s>>>(lrow, col, val, x, n_cols, ypart, extra, it, meta, bp, ph_lo)
+#define PCMX_SLICED(PACKED, PL) \
+    spmv_sliced_kernel<PACKED, PL><<<nb, blk, 0, s>>>(lrow, col, val, x, n_cols, ypart, extra, it, meta, bp, ph_lo)
         // slice_colbase != NULL: col holds the packed words (production layout when every slice is < 2^21 columns)
         if (slice_colbase) {
-#define PCMX_SLICED_TS(M, PL) spmv_sliced_kernel<M, PL, true><<<nb, blk, 0, s>>>(lrow, col, val, x, n_cols, ypart, extra, it, meta, bp, ph_lo)
-            const bool ts = !(mode & kModeNtPartials);
-            if (mode & kMode256)
-                (ts ? PCMX_SLICED_TS(12, 4) : PCMX_SLICED(12, 4));
-            else if (mode & kMode384)
-                (ts ? PCMX_SLICED_TS(12, 6) : PCMX_SLICED(12, 6));
-            else if ((mode & 7) == 2)
-                (ts ? PCMX_SLICED_TS(12, 8) : PCMX_SLICED(12, 8));
-            else if ((mode & 7) == 0)
-                (ts ? PCMX_SLICED_TS(12, 16) : PCMX_SLICED(12, 16));
-            else
-                return (int)hipErrorInvalidValue;  // the lab modes read the unpacked layout
-#undef PCMX_SLICED_TS
-        } else if (mode & (kMode256 | kMode384)) {
-            return (int)hipErrorInvalidValue;  // 256 / 384-nonzero items: packed layout only
-        } else switch (mode & 7) {
-            case 0: PCMX_SLICED(4, 16); break;
-            case 1: PCMX_SLICED(5, 16); break;
-            case 2: PCMX_SLICED(4, 8); break;
-            case 3: PCMX_SLICED(5, 8); break;
-            case 4: PCMX_SLICED(0, 16); break;
-            case 5: PCMX_SLICED(1, 16); break;
-            case 6: PCMX_SLICED(0, 8); break;
-            default: PCMX_SLICED(1, 8); break;
+            switch (item_nnz) {
+                case 256: PCMX_SLICED(true, 4); break;
+                case 384: PCMX_SLICED(true, 6); break;
+                case 512: PCMX_SLICED(true, 8); break;
+                default: PCMX_SLICED(true, 16); break;
+            }
+        } else if (item_nnz == 512) {
+            PCMX_SLICED(false, 8);
+        } else {
+            PCMX_SLICED(false, 16);
         }
 #undef PCMX_SLICED
     }
-    if (mode & 16) return (int)hipGetLastError();
+    if (stage == PCMX_SPMV_PRODUCTS) return (int)hipGetLastError();
     const unsigned cb = (unsigned)((n_rows + 2047) / 2048) * 8;  // 4 waves of 64 rows per block, 8k blocks
-    // bit 6 (lab): the ballot-rank combine instead of the byte-packed scan (bit-identical results); the scan form
-    // addresses the partials with 32-bit byte offsets
-    if (so.out0[n_slices] >= (1ll << 30)) mode |= 64;
+    // ballot_combine: the ballot-rank combine instead of the byte-packed scan (bit-identical results; the tests'
+    // oracle of the scan). The scan form addresses the partials with 32-bit byte offsets, so 2^30 partials or more
+    // take the ballot form whatever the caller asked for.
+    const bool ballot = ballot_combine || so.out0[n_slices] >= (1ll << 30);
 #define PCMX_COMBINE(K)                                                                                            \
     do {                                                                                                           \
-        if (mode & 64) spmv_combine_kernel<K><<<cb, 256, 0, s>>>(ypart, row_mask, chunk_base, so, y, n_rows);      \
+        if (ballot) spmv_combine_kernel<K><<<cb, 256, 0, s>>>(ypart, row_mask, chunk_base, so, y, n_rows);         \
         else spmv_combine_scan_kernel<K><<<cb, 256, 0, s>>>(ypart, row_mask, chunk_base, so, y, n_rows);           \
     } while (0)
     switch (n_slices) {
@@ -1072,19 +1023,18 @@ extern "C" int pcmx_spmv_sliced(const unsigned short* lrow, const int* col, cons
 // Round 5: the products (no combine) of phases [a_lo, a_lo + a_n) of sliced matrix A and [b_lo, b_lo + b_n) of sliced
 // matrix B — two matrices over the SAME x, e.g. the two row chunks of a distributed column-split step multiplying their
 // chunk-0 columns — in ONE launch: a launch of a few items per wave pays its ramp and tail once instead of twice.
-// Production layout only (packed index stream, temporal partial stores unless mode bit 26); item_mode 2 / 4 / 6: 512 / 256 / 384-nnz
-// items (0: 1024).
+// Production layout only (packed index stream); item_nnz 256 / 384 / 512 / 1024, the same for both matrices.
 // meta_*: host arrays nz0 (S), item0 (S + 1), out0 (S + 1), colbase (S) of each matrix.
-extern "C" int pcmx_spmv_sliced_pair(const float* x, int n_cols, int item_mode, int mode, const int* col_a,
+extern "C" int pcmx_spmv_sliced_pair(const float* x, int n_cols, int item_nnz, int blocks_per_cu, const int* col_a,
                                      const float* val_a, const void* items_a, float* ypart_a, float* extra_a, int s_a,
                                      const long long* nz0_a, const long long* item0_a, const long long* out0_a,
                                      const int* colbase_a, int a_lo, int a_n, const int* col_b, const float* val_b,
                                      const void* items_b, float* ypart_b, float* extra_b, int s_b,
                                      const long long* nz0_b, const long long* item0_b, const long long* out0_b,
                                      const int* colbase_b, int b_lo, int b_n, hipStream_t s) {
+    if (!sliced_item_ok(item_nnz, true) || !sliced_blocks_ok(blocks_per_cu)) return PCMX_ERR_ARG;
     if (s_a % 8 || s_b % 8 || a_lo < 0 || b_lo < 0 || a_n < 0 || b_n < 0 || 8 * (a_lo + a_n) > s_a ||
-        8 * (b_lo + b_n) > s_b || 8 * (a_n + b_n) > kMaxSlices ||
-        (item_mode != 0 && item_mode != 2 && item_mode != 4 && item_mode != 6))
+        8 * (b_lo + b_n) > s_b || 8 * (a_n + b_n) > kMaxSlices)
         return (int)hipErrorInvalidValue;
     if (a_n + b_n == 0) return 0;
     SliceMeta meta{};
@@ -1106,31 +1056,27 @@ extern "C" int pcmx_spmv_sliced_pair(const float* x, int n_cols, int item_mode, 
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         cus = 256;
-    const int persist_blocks = (mode >> 8) & 0xff ? (mode >> 8) & 0xff : kPersistBlocks;
+    const int persist_blocks = blocks_per_cu ? blocks_per_cu : kPersistBlocks;
     const long long need = (most + kWavesPerBlock - 1) / kWavesPerBlock;
     const long long per = (long long)(cus / 8) * persist_blocks;
     const int bp = (int)(need < per ? need : per);
     const unsigned nb = (unsigned)(bp * (m / 8) * 8);
     const Item* ia = reinterpret_cast<const Item*>(items_a);
     const dim3 blk(kWavesPerBlock * kWave);
-    const bool ts = !(mode & kModeNtPartials);
-#define PCMX_PAIR(PL, TS)                                                                                           \
-    spmv_sliced_kernel<12, PL, TS, true><<<nb, blk, 0, s>>>(nullptr, col_a, val_a, x, n_cols, ypart_a, extra_a, ia, meta, bp, \
-                                                             0)
-    if (item_mode == 4)
-        ts ? PCMX_PAIR(4, true) : PCMX_PAIR(4, false);
-    else if (item_mode == 6)
-        ts ? PCMX_PAIR(6, true) : PCMX_PAIR(6, false);
-    else if (item_mode == 2)
-        ts ? PCMX_PAIR(8, true) : PCMX_PAIR(8, false);
-    else
-        ts ? PCMX_PAIR(16, true) : PCMX_PAIR(16, false);
+#define PCMX_PAIR(PL) \
+    spmv_sliced_kernel<true, PL, true><<<nb, blk, 0, s>>>(nullptr, col_a, val_a, x, n_cols, ypart_a, extra_a, ia, meta, bp, 0)
+    switch (item_nnz) {
+        case 256: PCMX_PAIR(4); break;
+        case 384: PCMX_PAIR(6); break;
+        case 512: PCMX_PAIR(8); break;
+        default: PCMX_PAIR(16); break;
+    }
 #undef PCMX_PAIR
     return (int)hipGetLastError();
 }
 
 // Round 5: the combine + fix-up (+ send-buffer pack) of a sliced product in ONE launch (spmv_combine_fused_kernel), for
-// a caller that ran the products alone (pcmx_spmv_sliced with mode bit 4). slice_out0: n_slices + 1 partial offsets;
+// a caller that ran the products alone (pcmx_spmv_sliced with stage PCMX_SPMV_PRODUCTS). slice_out0: n_slices + 1 partial offsets;
 // fix_chunk0: n_rows / 64 + 2 entries (or null: no split rows); send_ptr / send_slot / sendbuf: the pack (or null).
 extern "C" int pcmx_spmv_sliced_combine(const float* ypart, const unsigned* row_mask, const int* chunk_base,
                                         const long long* slice_out0, int n_slices, float* y, int n_rows,
@@ -1232,12 +1178,12 @@ const pcmx::i32x4* banded_lut_table(const BandGeo& g, hipStream_t s) {
     ent.first = d;
     return reinterpret_cast<const pcmx::i32x4*>(d);
 }
-// Variant 8/9 launch (block stream over the unclipped rows, the clipped row blocks folded into the same grid);
+// Variant 8 launch (block stream over the unclipped rows, the clipped row blocks folded into the same grid);
 // kStreamNotApplicable when the band geometry or the value alignment rules it out.
-template <int RS, int NV, int XW>
 int launch_banded_stream(const float* vals, const long long* row_off, int n, int a, int b, int c, int d, int e,
                          const float* x, float* y, hipStream_t s) {
     // rows [rlo, rhi) are unclipped (every band inside [0, n)) and all hold L nonzeros
+    constexpr int RS = kBandedRows, NV = kStreamNV, XW = kStreamXW;
     const int ah = a / 2, r9 = ah + b + c + d + e;
     const int L = 2 * ah + 1 + 2 * c + 2 * e;
     const long long maxrow = L;
@@ -1277,57 +1223,40 @@ int launch_banded_stream(const float* vals, const long long* row_off, int n, int
         band_limits_host(n, a, b, c, d, e, r, lo, hi);
         for (int k = 0; k < 5; ++k) off0 += hi[k] - lo[k];
     }
-    spmv_banded_stream_kernel<RS, NV, XW><<<nfront + nback + rb_hi - rb_lo, 256, std::max(lds_rows, lds8), s>>>(
+    spmv_banded_stream_kernel<<<nfront + nback + rb_hi - rb_lo, 256, std::max(lds_rows, lds8), s>>>(
         vals, row_off, n, a, b, c, d, e, nfront, back0, nfront + nback, off0, g, lut_g, rb_lo, x, y);
     return (int)hipGetLastError();
 }
 }  // namespace
 
 extern "C" int pcmx_spmv_banded_variant(const float* vals, const long long* row_off, int n, int a, int b, int c, int d,
-                                        int e, const float* x, float* y, int variant, hipStream_t s);
-extern "C" int pcmx_spmv_banded_variant(const float* vals, const long long* row_off, int n, int a, int b, int c, int d,
                                         int e, const float* x, float* y, int variant, hipStream_t s) {
     if (n <= 0) return 0;
     if (a < 1 || b < 0 || c < 0 || d < 0 || e < 0) return PCMX_ERR_ARG;
     const long long maxrow = 2LL * (a / 2) + 1 + 2LL * c + 2LL * e;  // nonzeros of an unclipped row
     const int nl = (int)((maxrow + 63) / 64);
-    // variant 1 (default) R = 16 rows per block, 2 rows per wave in flight; 4: R 32 / U 2; 5: R 16 / U 4;
-    // 6: R 32 / U 4; 7: R 64 / U 2 (scripts/spmv_banded_lab.py); 8: block stream (16-B loads over each block's
-    // contiguous value range, spmv_banded_stream_kernel)
-    const int R = variant == 4 || variant == 6 ? 32 : variant == 7 ? 64 : 16;
-    const size_t lds = (size_t)(maxrow + 5 * (R - 1)) * sizeof(float);
+    // 0: one wave per row; 1: LDS-staged x windows, 16 rows per block, 2 rows per wave in flight; 8: block stream
+    // (16-B loads over each 16-row block's contiguous value range, spmv_banded_stream_kernel), the production path
+    if (variant != 0 && variant != 1 && variant != 8) return PCMX_ERR_ARG;
+    const size_t lds = (size_t)(maxrow + 5 * (kBandedRows - 1)) * sizeof(float);
     if (variant == 0 || nl > 16 || lds > 64 * 1024) {
         spmv_banded_kernel<<<(n + 3) / 4, 256, 0, s>>>(vals, row_off, n, a, b, c, d, e, x, y);
         return (int)hipGetLastError();
     }
-    const int grid = (n + R - 1) / R;
-    if (variant >= 8 && variant <= 11) {
-        // 8: 16-row blocks (production); lab: 9 = 32-row blocks (the per-block setup — x windows, slot table,
-        // barrier — amortised over twice the values, at 2x the value registers), 10 = 12-row, 11 = 24-row blocks
-        const int rc = variant == 8    ? launch_banded_stream<16, 10, 3>(vals, row_off, n, a, b, c, d, e, x, y, s)
-                       : variant == 9  ? launch_banded_stream<32, 20, 4>(vals, row_off, n, a, b, c, d, e, x, y, s)
-                       : variant == 10 ? launch_banded_stream<12, 8, 3>(vals, row_off, n, a, b, c, d, e, x, y, s)
-                                       : launch_banded_stream<24, 15, 3>(vals, row_off, n, a, b, c, d, e, x, y, s);
-        if (rc == kStreamNotApplicable) return pcmx_spmv_banded_variant(vals, row_off, n, a, b, c, d, e, x, y, 1, s);
-        return rc;
+    if (variant == 8) {
+        // (short rows, unaligned values, a stream capture or a failed table allocation: variant 1 runs instead)
+        const int rc = launch_banded_stream(vals, row_off, n, a, b, c, d, e, x, y, s);
+        if (rc != kStreamNotApplicable) return rc;
     }
-#define PCMX_BANDED(RR, UU)                                                                                            \
-    do {                                                                                                               \
-        if (nl <= 2) spmv_banded_lds_kernel<RR, 2, UU><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y);   \
-        else if (nl <= 4) spmv_banded_lds_kernel<RR, 4, UU><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y); \
-        else if (nl <= 6) spmv_banded_lds_kernel<RR, 6, UU><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y); \
-        else if (nl <= 8) spmv_banded_lds_kernel<RR, 8, UU><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y); \
-        else if (nl <= 10) spmv_banded_lds_kernel<RR, 10, UU><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y); \
-        else if (nl <= 12) spmv_banded_lds_kernel<RR, 12, UU><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y); \
-        else spmv_banded_lds_kernel<RR, 16, UU><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y);          \
-    } while (0)
-    switch (variant) {
-        case 4: PCMX_BANDED(32, 2); break;
-        case 5: PCMX_BANDED(16, 4); break;
-        case 6: PCMX_BANDED(32, 4); break;
-        case 7: PCMX_BANDED(64, 2); break;
-        default: PCMX_BANDED(16, 2); break;
-    }
+    const int grid = (n + kBandedRows - 1) / kBandedRows;
+#define PCMX_BANDED(NL) spmv_banded_lds_kernel<NL><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y)
+    if (nl <= 2) PCMX_BANDED(2);
+    else if (nl <= 4) PCMX_BANDED(4);
+    else if (nl <= 6) PCMX_BANDED(6);
+    else if (nl <= 8) PCMX_BANDED(8);
+    else if (nl <= 10) PCMX_BANDED(10);
+    else if (nl <= 12) PCMX_BANDED(12);
+    else PCMX_BANDED(16);
 #undef PCMX_BANDED
     return (int)hipGetLastError();
 }

@@ -1106,25 +1106,40 @@ at::Tensor spmv_csr(const at::Tensor& row_ptr, const at::Tensor& col, const at::
     return y;
 }
 
-// XCD-sliced CSR (see spmv.hip): meta is a CPU int64 tensor [2 * n_slices + 1] = slice nz0[n_slices] ++
-// slice item0[n_slices + 1]; ypart [n_slices * n_rows] and extra [n_items] are caller-owned scratch.
+namespace {
+// the named launch options of the sliced ops, refused here before anything is launched or written
+void check_sliced_options(const char* op, int64_t item_nnz, bool packed, int64_t blocks_per_cu) {
+    TORCH_CHECK(item_nnz == 1024 || item_nnz == 512 || (packed && (item_nnz == 384 || item_nnz == 256)), op,
+                ": item_nnz must be 512 or 1024 (256 or 384 with the packed layout), got ", item_nnz);
+    TORCH_CHECK(blocks_per_cu >= 0 && blocks_per_cu <= 255, op, ": blocks_per_cu must be 0 (default) .. 255, got ",
+                blocks_per_cu);
+}
+}  // namespace
+
+// XCD-sliced CSR (see spmv.hip): meta is a CPU int64 tensor [nz0 (S) | item0 (S + 1) | out0 (S + 1)]; ypart (every
+// compact partial) and extra [n_items] are caller-owned scratch. packed: col holds one word per nonzero (column offset
+// + head flag + row offset; lrow unused) and meta ends with colbase (S). stage: 0 all, 1 products only, 2 combine +
+// fix-up only (PCMX_SPMV_*); phase_n 0: all phases from phase_lo.
 at::Tensor spmv_sliced(const at::Tensor& lrow, const at::Tensor& col, const at::Tensor& val, const at::Tensor& x,
                        const at::Tensor& items, const at::Tensor& row_mask, const at::Tensor& chunk_base,
                        const at::Tensor& fix, const at::Tensor& meta, at::Tensor ypart, at::Tensor extra, int64_t n_rows,
-                       const c10::optional<at::Tensor>& out, int64_t mode) {
+                       const c10::optional<at::Tensor>& out, bool packed, int64_t item_nnz, int64_t stage,
+                       bool ballot_combine, int64_t blocks_per_cu, int64_t phase_lo, int64_t phase_n) {
     check_gpu(lrow, "lrow", at::kShort), check_gpu(col, "col", at::kInt), check_gpu(val, "val", at::kFloat);
     check_gpu(x, "x", at::kFloat), check_gpu(items, "items", at::kLong), check_gpu(fix, "fix", at::kInt);
     check_gpu(ypart, "ypart", at::kFloat), check_gpu(extra, "extra", at::kFloat);
     check_gpu(row_mask, "row_mask", at::kInt), check_gpu(chunk_base, "chunk_base", at::kInt);
     TORCH_CHECK(!meta.is_cuda() && meta.scalar_type() == at::kLong && meta.is_contiguous(), "spmv_sliced: CPU int64 meta");
-    // mode bit 3: packed layout (col holds one word per nonzero: column offset + head flag + row offset; lrow unused)
-    // and meta = [nz0 (S) | item0 (S + 1) | out0 (S + 1) | colbase (S)]; otherwise meta = [nz0 | item0 | out0]
-    const bool packed = (mode & 8) != 0;
+    check_sliced_options("spmv_sliced", item_nnz, packed, blocks_per_cu);
+    TORCH_CHECK(stage == PCMX_SPMV_ALL || stage == PCMX_SPMV_PRODUCTS || stage == PCMX_SPMV_COMBINE,
+                "spmv_sliced: stage must be 0 (all), 1 (products) or 2 (combine), got ", stage);
     const int64_t S = (meta.numel() - 2) / (packed ? 4 : 3);
     TORCH_CHECK(meta.numel() == (packed ? 4 : 3) * S + 2 && S >= 8 && S % 8 == 0 && S <= PCMX_SPMV_MAX_SLICES,
                 "spmv_sliced: 8, 16, 24 or 32 slices");
     const int64_t* m = meta.data_ptr<int64_t>();
     const int64_t* out0 = m + 2 * S + 1;
+    TORCH_CHECK(phase_lo >= 0 && phase_n >= 0 && phase_lo + phase_n <= S / 8 && phase_lo < S / 8,
+                "spmv_sliced: phases [", phase_lo, ", ", phase_lo + phase_n, ") outside the ", S / 8, " phases");
     TORCH_CHECK((packed || lrow.numel() == col.numel()) && val.numel() == col.numel(), "spmv_sliced: lrow / val shape");
     std::vector<int> colbase;
     if (packed) {
@@ -1132,9 +1147,6 @@ at::Tensor spmv_sliced(const at::Tensor& lrow, const at::Tensor& col, const at::
             TORCH_CHECK(m[3 * S + 2 + k] >= 0 && m[3 * S + 2 + k] < x.numel(), "spmv_sliced: packed column base");
             colbase.push_back((int)m[3 * S + 2 + k]);
         }
-        TORCH_CHECK((mode & 7) == 0 || (mode & 7) == 2, "spmv_sliced: the packed layout runs the production modes only");
-    } else {
-        TORCH_CHECK(!(mode & ((1 << 27) | (1 << 28))), "spmv_sliced: 256 / 384-nonzero items need the packed layout");
     }
     TORCH_CHECK(row_mask.numel() >= n_rows && chunk_base.numel() >= ((n_rows + 63) / 64) * S,
                 "spmv_sliced: row_mask / chunk_base shape");
@@ -1161,7 +1173,8 @@ at::Tensor spmv_sliced(const at::Tensor& lrow, const at::Tensor& col, const at::
                               y.data_ptr<float>(), (int)n_rows, (int)x.numel(), (int)S, (const long long*)m,
                               (const long long*)m + S, (const long long*)out0, items.data_ptr(),
                               reinterpret_cast<const unsigned*>(row_mask.data_ptr<int>()), chunk_base.data_ptr<int>(),
-                              fix.data_ptr(), (int)fix.size(0), (int)(mode & ~8), packed ? colbase.data() : nullptr,
+                              fix.data_ptr(), (int)fix.size(0), (int)item_nnz, (int)stage, (int)ballot_combine,
+                              (int)blocks_per_cu, (int)phase_lo, (int)phase_n, packed ? colbase.data() : nullptr,
                               cur_stream(val)),
              "spmv_sliced");
     return y;
@@ -1169,12 +1182,13 @@ at::Tensor spmv_sliced(const at::Tensor& lrow, const at::Tensor& col, const at::
 
 // Products only of phases [a_lo, a_lo + a_n) of sliced matrix A and [b_lo, b_lo + b_n) of B (same x), ONE launch
 // (pcmx_spmv_sliced_pair). meta_*: the packed spmv_sliced meta (nz0 S | item0 S + 1 | out0 S + 1 | colbase S).
-void spmv_sliced_pair(const at::Tensor& x, int64_t item_mode, int64_t mode, const at::Tensor& col_a,
+void spmv_sliced_pair(const at::Tensor& x, int64_t item_nnz, int64_t blocks_per_cu, const at::Tensor& col_a,
                       const at::Tensor& val_a, const at::Tensor& items_a, const at::Tensor& meta_a, at::Tensor ypart_a,
                       at::Tensor extra_a, int64_t s_a, int64_t a_lo, int64_t a_n, const at::Tensor& col_b,
                       const at::Tensor& val_b, const at::Tensor& items_b, const at::Tensor& meta_b, at::Tensor ypart_b,
                       at::Tensor extra_b, int64_t s_b, int64_t b_lo, int64_t b_n) {
     check_gpu(x, "x", at::kFloat);
+    check_sliced_options("spmv_sliced_pair", item_nnz, true, blocks_per_cu);
     TORCH_CHECK(x.numel() < (int64_t(1) << 30), "spmv_sliced_pair: x must be < 2^30 elements");
     auto chk = [&](const at::Tensor& col, const at::Tensor& val, const at::Tensor& items, const at::Tensor& meta,
                    const at::Tensor& ypart, const at::Tensor& extra, int64_t S, int64_t lo, int64_t n) {
@@ -1205,7 +1219,7 @@ void spmv_sliced_pair(const at::Tensor& x, int64_t item_mode, int64_t mode, cons
     const auto cba = cb(meta_a, s_a), cbb = cb(meta_b, s_b);
     const int64_t *ma = meta_a.data_ptr<int64_t>(), *mb = meta_b.data_ptr<int64_t>();
     const at::DeviceGuard g(x.device());
-    check_rc(pcmx_spmv_sliced_pair(x.data_ptr<float>(), (int)x.numel(), (int)item_mode, (int)mode, col_a.data_ptr<int>(),
+    check_rc(pcmx_spmv_sliced_pair(x.data_ptr<float>(), (int)x.numel(), (int)item_nnz, (int)blocks_per_cu, col_a.data_ptr<int>(),
                                    val_a.data_ptr<float>(), items_a.data_ptr(), ypart_a.data_ptr<float>(),
                                    extra_a.data_ptr<float>(), (int)s_a, (const long long*)ma, (const long long*)ma + s_a,
                                    (const long long*)ma + 2 * s_a + 1, cba.data(), (int)a_lo, (int)a_n,
@@ -1216,7 +1230,7 @@ void spmv_sliced_pair(const at::Tensor& x, int64_t item_mode, int64_t mode, cons
              "spmv_sliced_pair");
 }
 
-// The combine + fix-up (+ send-buffer pack) of the partials a products-only spmv_sliced call (mode bit 4) wrote, in one
+// The combine + fix-up (+ send-buffer pack) of the partials a products-only spmv_sliced call (stage 1) wrote, in one
 // launch (pcmx_spmv_sliced_combine). meta: the spmv_sliced meta of the same matrix (out0 at [2S + 1, 3S + 2)).
 void spmv_sliced_combine(const at::Tensor& ypart, const at::Tensor& row_mask, const at::Tensor& chunk_base,
                          const at::Tensor& meta, int64_t n_slices, const at::Tensor& extra, const at::Tensor& fix,
@@ -1374,8 +1388,8 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("stencil5xT_(Tensor u, Tensor(a!) out, int halo, int steps, int r0, int r1, int global_row0, int global_rows, float k, int shape=0) -> ()");
     m.def("stencil5xT_spans_(Tensor u, Tensor(a!) out, int halo, int steps, int r0a, int r1a, int r0b, int r1b, int global_row0, int global_rows, float k, int shape=0) -> ()");
     m.def("spmv_csr(Tensor row_ptr, Tensor col, Tensor val, Tensor x, Tensor items) -> Tensor");
-    m.def("spmv_sliced(Tensor lrow, Tensor col, Tensor val, Tensor x, Tensor items, Tensor row_mask, Tensor chunk_base, Tensor fix, Tensor meta, Tensor(a!) ypart, Tensor(b!) extra, int n_rows, Tensor(c!)? out=None, int mode=0) -> Tensor");
-    m.def("spmv_sliced_pair(Tensor x, int item_mode, int mode, Tensor col_a, Tensor val_a, Tensor items_a, Tensor meta_a, Tensor(a!) ypart_a, Tensor(b!) extra_a, int s_a, int a_lo, int a_n, Tensor col_b, Tensor val_b, Tensor items_b, Tensor meta_b, Tensor(c!) ypart_b, Tensor(d!) extra_b, int s_b, int b_lo, int b_n) -> ()");
+    m.def("spmv_sliced(Tensor lrow, Tensor col, Tensor val, Tensor x, Tensor items, Tensor row_mask, Tensor chunk_base, Tensor fix, Tensor meta, Tensor(a!) ypart, Tensor(b!) extra, int n_rows, Tensor(c!)? out=None, bool packed=False, int item_nnz=1024, int stage=0, bool ballot_combine=False, int blocks_per_cu=0, int phase_lo=0, int phase_n=0) -> Tensor");
+    m.def("spmv_sliced_pair(Tensor x, int item_nnz, int blocks_per_cu, Tensor col_a, Tensor val_a, Tensor items_a, Tensor meta_a, Tensor(a!) ypart_a, Tensor(b!) extra_a, int s_a, int a_lo, int a_n, Tensor col_b, Tensor val_b, Tensor items_b, Tensor meta_b, Tensor(c!) ypart_b, Tensor(d!) extra_b, int s_b, int b_lo, int b_n) -> ()");
     m.def("spmv_sliced_combine(Tensor ypart, Tensor row_mask, Tensor chunk_base, Tensor meta, int n_slices, Tensor extra, Tensor fix, Tensor? fix_chunk0, Tensor(a!) out, int n_rows, Tensor? send_ptr=None, Tensor? send_slot=None, Tensor(b!)? sendbuf=None) -> ()");
     m.def("spmv_banded(Tensor vals, Tensor row_off, int n, int a, int b, int c, int d, int e, Tensor x, int variant=8) -> Tensor");
     m.def("pack_edges(Tensor tile) -> Tensor");

@@ -83,8 +83,6 @@ class SlicedCSR:
         if item_nnz not in (256, 384, 512, 1024):
             raise ValueError("item_nnz must be 256, 384, 512 or 1024 (4, 6, 8 or 16 nonzeros per lane)")
         self.item_nnz = item_nnz
-        # kernel layout bits: items of 512 nonzeros (bit 1), of 256 (bit 27) or 384 (bit 28; both packed layout only)
-        self.mode = {512: 2, 256: 1 << 27, 384: 1 << 28}.get(item_nnz, 0)
         dev = m.val.device
         n, S, nnz = m.n_rows, n_slices, m.nnz
         self.n_rows, self.n_cols, self.n_slices, self.nnz = n, m.n_cols, S, nnz
@@ -208,7 +206,7 @@ class SlicedCSR:
         b = self.bounds.tolist()
         lo, hi = [0] + b, b + [self.n_cols]
         self.colbase = lo
-        self.cr = None
+        self.cr = self._meta_packed = self._no_lrow = None
         if not pack or self.nnz == 0 or H >= 1 << 21 or max(h - l for l, h in zip(lo, hi)) >= 1 << 21:
             return
         dev = self.col.device
@@ -216,6 +214,9 @@ class SlicedCSR:
         c = self.col.long()
         w = torch.where(c < H, c | (1 << 21), c - torch.tensor(lo, device=dev)[sid]) | (self.lrow.long() << 22)
         self.cr = (w - ((w >> 31) << 32)).to(torch.int32)  # two's-complement wrap of the 32-bit word
+        # what the ops read with the packed layout: the meta with the slices' first tail columns, and no lrow
+        self._meta_packed = torch.cat([self.meta, torch.tensor(lo, dtype=torch.int64)]).contiguous()
+        self._no_lrow = torch.empty(0, dtype=torch.int16, device=dev)
 
     @property
     def partials(self) -> int:
@@ -223,20 +224,18 @@ class SlicedCSR:
         return int(self.meta[-1])
 
     def products_pair(self, other: SlicedCSR, x: torch.Tensor, phases: tuple[int, int],
-                      other_phases: tuple[int, int], mode: int = 0) -> None:
+                      other_phases: tuple[int, int], blocks_per_cu: int = 0) -> None:
         """The products (no combine) of phases `phases` = (lo, n) of this matrix and `other_phases` of `other` (another
         sliced matrix over the same x) in ONE launch; each matrix then combines its own partials as after a
-        products-only call (the distributed column-split step's two row chunks, chunk-0 columns)."""
-        for m in (self, other):
-            if m.cr is None:
-                raise ValueError("products_pair: packed index stream only")
-            if getattr(m, "_meta_packed", None) is None:
-                m._meta_packed = torch.cat([m.meta, torch.tensor(m.colbase, dtype=torch.int64)]).contiguous()
-                m._no_lrow = torch.empty(0, dtype=torch.int16, device=m.cr.device)
-        if self.mode != other.mode:
+        products-only call (the distributed column-split step's two row chunks, chunk-0 columns). blocks_per_cu:
+        resident product blocks per CU (0: the library default, 3)."""
+        if self.cr is None or other.cr is None:
+            raise ValueError("products_pair: packed index stream only")
+        if self.item_nnz != other.item_nnz:
             raise ValueError("products_pair: both matrices need the same item size")
-        item_mode = 4 if self.mode & (1 << 27) else 6 if self.mode & (1 << 28) else self.mode
-        ops().spmv_sliced_pair(x, item_mode, int(mode), self.cr, self.val, self.items, self._meta_packed, self.ypart,
+        if not 0 <= int(blocks_per_cu) <= 255:
+            raise ValueError(f"blocks_per_cu {blocks_per_cu} outside 0..255")
+        ops().spmv_sliced_pair(x, self.item_nnz, int(blocks_per_cu), self.cr, self.val, self.items, self._meta_packed, self.ypart,
                                self.extra, self.n_slices, int(phases[0]), int(phases[1]), other.cr, other.val,
                                other.items, other._meta_packed, other.ypart, other.extra, other.n_slices,
                                int(other_phases[0]), int(other_phases[1]))
@@ -245,7 +244,7 @@ class SlicedCSR:
         """The combine + split-row fix-up of the partials the last products-only call wrote, into out[:n_rows], in ONE
         launch; send = (send_ptr, send_slot, sendbuf): also write every row's value into the send-buffer slots that
         carry it to the peers (the distributed step's pack, fused into the same launch)."""
-        meta = self._meta_packed if getattr(self, "_meta_packed", None) is not None else self.meta
+        meta = self._meta_packed if self.cr is not None else self.meta
         sp, ss, sb = send if send is not None else (None, None, None)
         if send is not None:
             self._check_send(sp, ss, sb)
@@ -271,36 +270,40 @@ class SlicedCSR:
             raise ValueError("send: send_ptr must rise from 0 to len(send_slot) and every slot must lie in sendbuf")
         self._send_ok = getattr(self, "_send_ok", set()) | {key}
 
-    def spmv(self, x: torch.Tensor, out: torch.Tensor | None = None, mode: int = 0,
-             phases: tuple[int, int] | None = None, send: tuple | None = None) -> torch.Tensor:
-        """y = A x; `out` (contiguous f32, >= n_rows elements) receives y in place when given. mode bit 4: products
-        only (compact partials, no combine), bit 5: combine + fix-up only (of the partials a bit-4 call wrote).
+    _STAGES = {"all": 0, "products": 1, "combine": 2}  # PCMX_SPMV_ALL / _PRODUCTS / _COMBINE
+
+    def spmv(self, x: torch.Tensor, out: torch.Tensor | None = None, stage: str = "all", combine: str = "scan",
+             blocks_per_cu: int = 0, phases: tuple[int, int] | None = None, send: tuple | None = None) -> torch.Tensor:
+        """y = A x; `out` (contiguous f32, >= n_rows elements) receives y in place when given.
+        stage: "products" writes the compact partials only (no combine), "combine" runs the combine + fix-up of the
+        partials a products call wrote, "all" both. combine: "scan" (the byte-packed scan, production) or "ballot" (the
+        ballot-rank form, same bits). blocks_per_cu: resident product blocks per CU (0: the library default, 3).
         phases=(lo, n): the products of slices [8 lo, 8 (lo + n)) only (one slice per XCD per phase) — with col_split,
-        phases (0, S/16) multiply the columns below the split and (S/16, S/16) the others. A combining call runs the
-        fused combine (combine + fix-up in one launch, and the send-buffer pack when `send` is given; see combine())."""
-        if self.fused_combine and not (mode & 16) and (mode & ~32 & 0xCF) == 0 and self.cr is not None:
+        phases (0, S/16) multiply the columns below the split and (S/16, S/16) the others. With `fused_combine` set, a
+        combining call on the packed layout with the scan combine runs the fused combine (combine + fix-up in one
+        launch, and the send-buffer pack when `send` is given; see combine())."""
+        if stage not in self._STAGES:
+            raise ValueError(f"stage {stage!r}: one of {sorted(self._STAGES)}")
+        if combine not in ("scan", "ballot"):
+            raise ValueError(f"combine {combine!r}: 'scan' or 'ballot'")
+        if not 0 <= int(blocks_per_cu) <= 255:
+            raise ValueError(f"blocks_per_cu {blocks_per_cu} outside 0..255")
+        lo, n = phases if phases is not None else (0, 0)
+        if phases is not None and not (0 <= lo and 0 < n and lo + n <= self.n_slices // 8):
+            raise ValueError(f"phases {phases} outside the {self.n_slices // 8} phases")
+        packed = self.cr is not None
+        if self.fused_combine and stage != "products" and combine == "scan" and packed:
             if out is None:
                 out = torch.empty(self.n_rows, dtype=torch.float32, device=x.device)
-            if not (mode & 32):
-                self.spmv(x, mode=mode | 16, phases=phases)
+            if stage == "all":
+                self.spmv(x, stage="products", blocks_per_cu=blocks_per_cu, phases=phases)
             return self.combine(out, send)
         if send is not None:
             raise ValueError("send: the fused combine only (production layout)")
-        if phases is not None:
-            lo, n = phases
-            if not (0 <= lo and 0 < n and lo + n <= self.n_slices // 8):
-                raise ValueError(f"phases {phases} outside the {self.n_slices // 8} phases")
-            mode |= (lo << 16) | (n << 21)
-        # production: packed index stream (bit 6: ballot combine, 8+: resident blocks, 16-25: phases, 26: nt partials)
-        if self.cr is not None and (mode & 0x8F) == 0:
-            if getattr(self, "_meta_packed", None) is None:
-                self._meta_packed = torch.cat([self.meta, torch.tensor(self.colbase, dtype=torch.int64)]).contiguous()
-                self._no_lrow = torch.empty(0, dtype=torch.int16, device=self.cr.device)
-            return ops().spmv_sliced(self._no_lrow, self.cr, self.val, x, self.items, self.row_mask, self.chunk_base,
-                                     self.fix, self._meta_packed, self.ypart, self.extra, self.n_rows, out,
-                                     8 | self.mode | mode)
-        return ops().spmv_sliced(self.lrow, self.col, self.val, x, self.items, self.row_mask, self.chunk_base, self.fix,
-                                 self.meta, self.ypart, self.extra, self.n_rows, out, mode | self.mode)
+        lrow, col, meta = (self._no_lrow, self.cr, self._meta_packed) if packed else (self.lrow, self.col, self.meta)
+        return ops().spmv_sliced(lrow, col, self.val, x, self.items, self.row_mask, self.chunk_base, self.fix, meta,
+                                 self.ypart, self.extra, self.n_rows, out, packed, self.item_nnz, self._STAGES[stage],
+                                 combine == "ballot", int(blocks_per_cu), int(lo), int(n))
 
     def touched_rows(self, k: int) -> torch.Tensor:
         """Rows slice k touches (ascending), from the row mask."""

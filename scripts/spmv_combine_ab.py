@@ -1,5 +1,5 @@
-"""SpMV combine A/B (one MI355X, 1e8-nnz power-law, production sliced layout): the ballot-rank combine (mode bit 6)
-against the byte-packed-scan combine (default), each timed ALONE on the partials one product wrote (mode bit 5 =
+"""SpMV combine A/B (one MI355X, 1e8-nnz power-law, production sliced layout): the ballot-rank combine (combine="ballot")
+against the byte-packed-scan combine (default), each timed ALONE on the partials one product wrote (stage="combine":
 combine + fix-up only), plus the whole product both ways; the two y must be bit-identical.
 Run: python scripts/spmv_combine_ab.py [slices ...]"""
 import os
@@ -35,14 +35,14 @@ for S in [int(a) for a in sys.argv[1:]] or [24, 16]:
     s = ops.SlicedCSR(m, S, head=0.0625, item_nnz=1024)
     ref = s.reference(x)
     y_scan = s.spmv(x).clone()
-    y_ballot = s.spmv(x, mode=64).clone()
+    y_ballot = s.spmv(x, combine="ballot").clone()
     same = torch.equal(y_scan, y_ballot)
     err = ((y_scan.double() - ref).abs().max() / ref.abs().max()).item()
-    s.spmv(x, mode=16)  # partials for the combine-only timings
-    t_scan = timed(lambda: s.spmv(x, mode=32))
-    t_ballot = timed(lambda: s.spmv(x, mode=32 | 64))
+    s.spmv(x, stage="products")  # partials for the combine-only timings
+    t_scan = timed(lambda: s.spmv(x, stage="combine"))
+    t_ballot = timed(lambda: s.spmv(x, stage="combine", combine="ballot"))
     p_scan = timed(lambda: s.spmv(x))
-    p_ballot = timed(lambda: s.spmv(x, mode=64))
+    p_ballot = timed(lambda: s.spmv(x, combine="ballot"))
     print(f"slices {S}: partials {s.partials}  combine+fixup ballot {t_ballot * 1e3:.1f} us  scan {t_scan * 1e3:.1f} us"
           f"  | product ballot {p_ballot:.4f} ms ({2 * nnz / p_ballot / 1e6:.1f} GFLOP/s)  scan {p_scan:.4f} ms"
           f" ({2 * nnz / p_scan / 1e6:.1f} GFLOP/s)  bit-identical {same}  err {err:.1e}", flush=True)

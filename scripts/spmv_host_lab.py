@@ -72,20 +72,20 @@ def main():
         if kind == "paired_side":  # paired, with row chunk 0's combine + pack on a side stream beside chunk 1's products
             (_, _, p0), (_, _, p1) = d.parts
             half = p0.n_slices // 16
-            p0.products_pair(p1, xp, (0, half), (0, p1.n_slices // 16), mode=p0.phase_blocks[0] << 8)
+            p0.products_pair(p1, xp, (0, half), (0, p1.n_slices // 16), blocks_per_cu=p0.phase_blocks[0])
             main = torch.cuda.current_stream(dev)
-            p0.spmv(xp, mode=16 | (p0.phase_blocks[1] << 8), phases=(half, half))
+            p0.spmv(xp, stage="products", blocks_per_cu=p0.phase_blocks[1], phases=(half, half))
             side.wait_stream(main)
             s0, (a0, b0, _) = d.seg[0 * Wd + r], d.parts[0]
             with torch.cuda.stream(side):
-                p0.spmv(xp, out[s0:s0 + (b0 - a0)], mode=32, send=send_csr[0])
+                p0.spmv(xp, out[s0:s0 + (b0 - a0)], stage="combine", send=send_csr[0])
             s1, (a1, b1, _) = d.seg[1 * Wd + r], d.parts[1]
             p1.product_phase(xp, 1, 1, out[s1:s1 + (b1 - a1)], send=send_csr[1])
             main.wait_stream(side)
             return
         if kind == "paired":
             (_, _, p0), (_, _, p1) = d.parts
-            p0.products_pair(p1, xp, (0, p0.n_slices // 16), (0, p1.n_slices // 16), mode=p0.phase_blocks[0] << 8)
+            p0.products_pair(p1, xp, (0, p0.n_slices // 16), (0, p1.n_slices // 16), blocks_per_cu=p0.phase_blocks[0])
         else:
             for c, (a, b, part) in enumerate(d.parts):
                 if b > a:
@@ -183,7 +183,7 @@ def main():
             if pend[0] is not None:
                 pend[0].wait()
                 pend[0] = None
-            q0.products_pair(q1, xp, (0, q0.n_slices // 16), (0, q1.n_slices // 16), mode=q0.phase_blocks[0] << 8)
+            q0.products_pair(q1, xp, (0, q0.n_slices // 16), (0, q1.n_slices // 16), blocks_per_cu=q0.phase_blocks[0])
             if pend[1] is not None:
                 pend[1].wait()
                 pend[1] = None

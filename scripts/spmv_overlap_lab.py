@@ -37,21 +37,19 @@ def main():
         dsts = [torch.empty(max(1, b - a), device=dev) for a, b, _ in d.parts]
         ref = d.reference_local(xp)
         for pb in (0, 2, 3, 4):
-            hi = pb << 8
-
             def serial():
                 for (a, b, part), dst in zip(d.parts, dsts):
-                    part.spmv(xp, dst[:b - a], hi)
+                    part.spmv(xp, dst[:b - a], blocks_per_cu=pb)
 
             def overlap():
                 main = torch.cuda.current_stream(dev)
                 for (a, b, part), dst in zip(d.parts, dsts):
-                    part.spmv(xp, dst[:b - a], hi | 16)
+                    part.spmv(xp, dst[:b - a], stage="products", blocks_per_cu=pb)
                     ev = torch.cuda.Event()
                     ev.record(main)
                     side.wait_event(ev)
                     with torch.cuda.stream(side):
-                        part.spmv(xp, dst[:b - a], 32)
+                        part.spmv(xp, dst[:b - a], stage="combine")
                 ev = torch.cuda.Event()
                 ev.record(side)
                 main.wait_event(ev)

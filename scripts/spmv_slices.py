@@ -18,30 +18,26 @@ s = d.parts[0][2]  # one rank, one chunk: the whole matrix
 x = torch.rand(s.n_cols, device="cuda")
 
 
-MODE = 0
-
-
-def bench(meta, reps=20):
-    for _ in range(3):
+def bench(meta, blocks_per_cu=0, reps=20):
+    """The whole product on the unpacked arrays with `meta` (nz0 | item0 | out0) in place of the matrix's own."""
+    def run():
         native().spmv_sliced(s.lrow, s.col, s.val, x, s.items, s.row_mask, s.chunk_base, s.fix, meta, s.ypart, s.extra,
-                             s.n_rows, None, MODE | s.mode)
+                             s.n_rows, None, False, s.item_nnz, blocks_per_cu=blocks_per_cu)
+
+    for _ in range(3):
+        run()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(reps):
-        native().spmv_sliced(s.lrow, s.col, s.val, x, s.items, s.row_mask, s.chunk_base, s.fix, meta, s.ypart, s.extra,
-                             s.n_rows, None, MODE | s.mode)
+        run()
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 
 
-for mode, what in [(1 | 2 << 8, "no x gathers"), (1 << 8, "1 block/CU"), (2 << 8, "2 blocks/CU"),
-                   (3 << 8, "3 blocks/CU"), (4 << 8, "4 blocks/CU"), (5 << 8, "5 blocks/CU"), (6 << 8, "6 blocks/CU"),
-                   (1 | 5 << 8, "no x gathers, 5 blocks/CU"), (4 | 2 << 8, "LDS row sums, 2 blocks/CU"),
-                   (4 | 5 << 8, "LDS row sums, 5 blocks/CU")]:
-    MODE = mode
-    print(f"mode {mode} ({what}): {bench(s.meta):.3f} ms")
-MODE = 0
+# (the "no x gathers" and "LDS row sums" rows of rounds 2-3 timed kernel paths that are gone: profiles/r2_spmv/)
+for blocks in (1, 2, 3, 4, 5, 6):
+    print(f"{blocks} block(s)/CU: {bench(s.meta, blocks):.3f} ms")
 full = bench(s.meta)
 if "--no-slices" in sys.argv:
     print(f"S={S} head={HEAD} item_nnz={ITEM} all slices: {full:.3f} ms  compact partials {s.partials}")

@@ -1,5 +1,5 @@
 """SpMV tuning lab (one MI355X, 1e8-nnz power-law, packed production kernel): slices x item size x resident
-blocks per CU (mode bits 8+), whole product time; every variant checked against the fp64 layout reference.
+blocks per CU (blocks_per_cu), whole product time; every variant checked against the fp64 layout reference.
 Run: python scripts/spmv_tune_lab.py"""
 import os
 import sys
@@ -35,9 +35,9 @@ for S in (24, 32):
         s = ops.SlicedCSR(m, S, head=0.0625, item_nnz=item)
         ref = s.reference(x)
         for pb in (2, 3, 4, 5):
-            y = s.spmv(x, mode=pb << 8).double()
+            y = s.spmv(x, blocks_per_cu=pb).double()
             err = ((y - ref).abs().max() / ref.abs().max()).item()
-            ms = timed(lambda: s.spmv(x, mode=pb << 8))
+            ms = timed(lambda: s.spmv(x, blocks_per_cu=pb))
             print(f"slices {S} item {item:4d} blocks/CU {pb}: {ms:.4f} ms {2 * nnz / ms / 1e6:.1f} GFLOP/s err {err:.1e}",
                   flush=True)
         del s

@@ -1,5 +1,7 @@
 """GPU numerics of the image/volume/stencil/sparse/halo kernels against the host C oracles and plain
 PyTorch references (GPU only)."""
+import functools
+
 import pytest
 import torch
 
@@ -371,9 +373,9 @@ def test_stencil_fused_spans_match_full(gpu, steps, spans):
                                   (4000, 1301, 10, 200, 10, 50), (20000, 401, 200, 100, 200, 10),
                                   (3001, 301, 10, 50, 10, 3), (1500, 401, 200, 100, 200, 10)])
 def test_spmv_banded_variants_vs_host(gpu, dims):
-    """Every banded kernel variant (0: wave per row; 1/4-7: LDS-staged windows, 4-B loads, block rows x rows in
-    flight; 8 / 9 / 10 / 11: block stream of 16 / 32 / 12 / 24 rows, 16-B loads over each row block's contiguous values) against the host product: interior
-    rows, rows clipped at both matrix edges (n smaller than the band reach: variant 8 then runs the variant-1 body in
+    """Every banded kernel variant (0: wave per row; 1: LDS-staged windows, 4-B loads, 16 rows per block, 2 rows per
+    wave in flight; 8: block stream of 16 rows, 16-B loads over each row block's contiguous values) against the host
+    product: interior rows, rows clipped at both matrix edges (n smaller than the band reach: variant 8 then runs the variant-1 body in
     every block), a row block past the last row, rows longer than 16 x 64 nonzeros (1301 + 400 + 100: the dispatcher
     falls back to the wave-per-row kernel), and rows shorter than 256 nonzeros (variant 8 falls back to 1)."""
     n = dims[0]
@@ -381,9 +383,35 @@ def test_spmv_banded_variants_vs_host(gpu, dims):
     x = ops.create_vector(n)
     ref = ops.spmv(m, x)
     vals, ro, xg = m.val.to(gpu), m.row_ptr.to(gpu), x.to(gpu)
-    for v in (0, 1, 4, 5, 6, 7, 8, 9, 10, 11):
+    for v in (0, 1, 8):
         out = ops.spmv_banded(vals, ro, *dims, xg, variant=v).cpu()
         assert (out - ref).abs().max().item() < 1e-3 * max(1.0, ref.abs().max().item()), (v, dims)
+
+
+def test_spmv_banded_rejects_removed_variants(gpu):
+    """Only variants 0, 1 and 8 exist: every other value (the removed lab variants 2-7 and 9-11 among them) raises
+    through the op, and is PCMX_ERR_ARG at the C entry point with y left as it was."""
+    import ctypes
+    import re
+    from pathlib import Path
+
+    from parallel_c_programs_amd._native import hip_lib
+
+    dims = (50, 9, 3, 5, 2, 3)
+    m = ops.banded_csr(*dims)
+    vals, ro, xg = m.val.to(gpu), m.row_ptr.to(gpu), ops.create_vector(dims[0]).to(gpu)
+    header = Path(__file__).resolve().parents[1] / "csrc" / "include" / "pcmx_errors.h"
+    err_arg = int(re.search(r"PCMX_ERR_ARG\s*=\s*(-?\d+)", header.read_text()).group(1))
+    lib = hip_lib()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for v in (-1, 2, 3, 4, 5, 6, 7, 9, 10, 11):
+        with pytest.raises(RuntimeError):
+            ops.spmv_banded(vals, ro, *dims, xg, variant=v)
+        y = torch.full((dims[0],), -7.0, device=gpu)
+        rc = lib.pcmx_spmv_banded_variant(ctypes.c_void_p(vals.data_ptr()), ctypes.c_void_p(ro.data_ptr()), *dims,
+                                          ctypes.c_void_p(xg.data_ptr()), ctypes.c_void_p(y.data_ptr()), v, stream)
+        assert rc == err_arg, v
+        assert torch.equal(y, torch.full_like(y, -7.0)), v
 
 
 def test_spmv_banded_stream_unaligned_values_fall_back(gpu):
@@ -508,9 +536,15 @@ def test_spmv_long_rows(gpu):
     assert (out - ref).abs().max().item() < 1e-3
 
 
+@functools.lru_cache(maxsize=None)
+def _powerlaw_30k():
+    """The 30000-row, 600k-nnz power-law matrix of the sliced-product tests (host CSR, read only)."""
+    return ops.powerlaw_csr(30000, 600_000, alpha=2.2, seed=5)
+
+
 @pytest.mark.parametrize("slices,head", [(8, 0.0), (16, 0.0625), (24, 0.0), (32, 0.2)])
 def test_spmv_sliced_powerlaw_vs_fp64(gpu, slices, head):
-    m = ops.powerlaw_csr(30000, 600_000, alpha=2.2, seed=5)
+    m = _powerlaw_30k()
     x = torch.rand(30000, dtype=torch.float32)
     ref = ops.SlicedCSR(m, slices, head=head).reference(x)  # layout oracle (CPU)
     rows = torch.repeat_interleave(torch.arange(m.n_rows), m.row_ptr[1:] - m.row_ptr[:-1])
@@ -529,9 +563,9 @@ def test_spmv_sliced_powerlaw_vs_fp64(gpu, slices, head):
     unpacked = ops.SlicedCSR(m.to(gpu), slices, head=head, pack=False)
     assert unpacked.cr is None
     assert torch.equal(out, unpacked.spmv(x.to(gpu)).cpu().double())
-    # byte-packed-scan combine (production) vs the ballot-rank combine (mode bit 6): same partials, same order
-    assert torch.equal(out, s.spmv(x.to(gpu), mode=64).cpu().double())
-    assert torch.equal(out, unpacked.spmv(x.to(gpu), mode=64).cpu().double())
+    # byte-packed-scan combine (production) vs the ballot-rank combine: same partials, same order
+    assert torch.equal(out, s.spmv(x.to(gpu), combine="ballot").cpu().double())
+    assert torch.equal(out, unpacked.spmv(x.to(gpu), combine="ballot").cpu().double())
     # the short items of distributed ranks (384 / 256 nonzeros, 6 / 4 per lane; packed layout only): fp64 bound,
     # reproducible
     for item in (384, 256):
@@ -539,6 +573,104 @@ def test_spmv_sliced_powerlaw_vs_fp64(gpu, slices, head):
         oi = si.spmv(x.to(gpu)).cpu().double()
         assert torch.equal(oi, si.spmv(x.to(gpu)).cpu().double())
         assert ((oi - want).abs() / (absrow + 1e-3)).max().item() < 1e-5, item
+
+
+@pytest.mark.parametrize("pack,item_nnz", [(True, 256), (True, 384), (True, 512), (True, 1024), (False, 512),
+                                           (False, 1024)])
+def test_spmv_sliced_stages_bit_identical(gpu, pack, item_nnz):
+    """The staged product of a column-split matrix — stage="products" over phases (0, 1) then (1, 1), then
+    stage="combine" — gives the bits of the one-call product, for both combines and with 0 (default) and 1 resident
+    blocks per CU; the six (layout, item size) cases run every product kernel. The partials are poisoned before the
+    staged calls, so a stage that skipped work cannot pass. On the packed layout, products_pair over the two halves of a
+    row split writes exactly the partials of the two separate products-only calls."""
+    m = _powerlaw_30k()
+    x = torch.rand(30000, generator=torch.Generator().manual_seed(3)).to(gpu)
+    s = ops.SlicedCSR(m.to(gpu), 16, item_nnz=item_nnz, pack=pack, col_split=15000)
+    assert (s.cr is not None) == pack and s.fused_combine is False
+    for combine in ("scan", "ballot"):
+        for blocks in (0, 1):
+            ref = s.spmv(x, combine=combine, blocks_per_cu=blocks).clone()
+            s.ypart.fill_(float("nan")), s.extra.fill_(float("nan"))
+            out = torch.full_like(ref, float("nan"))
+            s.spmv(x, stage="products", blocks_per_cu=blocks, phases=(0, 1))
+            s.spmv(x, stage="products", blocks_per_cu=blocks, phases=(1, 1))
+            assert torch.isnan(out).all()  # products only: nothing combined yet
+            got = s.spmv(x, out, stage="combine", combine=combine)
+            assert got.data_ptr() == out.data_ptr() and torch.equal(out, ref), (combine, blocks)
+    if not pack:
+        return
+    half = [ops.SlicedCSR(m.row_block(a, b).to(gpu), 16, item_nnz=item_nnz, col_split=15000)
+            for a, b in ((0, 15000), (15000, 30000))]
+    for blocks in (0, 1):
+        want = []
+        for h in half:
+            h.ypart.fill_(-7.0), h.extra.fill_(-7.0)
+            h.spmv(x, stage="products", blocks_per_cu=blocks, phases=(0, 1))
+            want.append((h.ypart.clone(), h.extra.clone()))
+            h.ypart.fill_(-7.0), h.extra.fill_(-7.0)
+        half[0].products_pair(half[1], x, (0, 1), (0, 1), blocks_per_cu=blocks)
+        for h, (yp, ex) in zip(half, want):
+            assert not torch.equal(yp, torch.full_like(yp, -7.0))
+            assert torch.equal(h.ypart, yp) and torch.equal(h.extra, ex), blocks
+
+
+def test_spmv_sliced_refuses_bad_launch_options(gpu):
+    """An unknown stage or combine, blocks_per_cu outside 0..255, phases outside the matrix, 256-nonzero items without
+    the packed layout and send= without the fused combine all raise, and `out` keeps its sentinel."""
+    from parallel_c_programs_amd.ops.sparse import PackedLayoutUnavailable
+
+    m = ops.powerlaw_csr(2000, 20_000, alpha=2.2, seed=9)
+    x = torch.rand(2000, device=gpu)
+    s = ops.SlicedCSR(m.to(gpu), 16, col_split=1000)
+    u = ops.SlicedCSR(m.to(gpu), 16, item_nnz=512, pack=False, col_split=1000)
+    ref_u = u.spmv(x).clone()
+    out = torch.full((2000,), -7.0, device=gpu)
+    send = (torch.zeros(2001, dtype=torch.int32, device=gpu), torch.zeros(0, dtype=torch.int32, device=gpu),
+            torch.zeros(1, device=gpu))
+    bad = [dict(stage="product"), dict(stage=1), dict(combine="dpp"), dict(combine=None), dict(blocks_per_cu=-1),
+           dict(blocks_per_cu=256), dict(phases=(2, 1)), dict(phases=(0, 3)), dict(phases=(-1, 1)), dict(phases=(1, 0)),
+           dict(send=send)]
+    for mat in (s, u):
+        for kw in bad:
+            with pytest.raises(ValueError):
+                mat.spmv(x, out, **kw)
+            assert torch.equal(out, torch.full_like(out, -7.0)), kw
+    with pytest.raises(PackedLayoutUnavailable):
+        ops.SlicedCSR(m.to(gpu), 16, item_nnz=256, pack=False, col_split=1000)
+    # the op itself refuses what SlicedCSR never builds: short items on the unpacked arrays, a stage outside 0..2
+    u.item_nnz = 256
+    with pytest.raises(RuntimeError):
+        u.spmv(x, out)
+    u.item_nnz = 512
+    u._STAGES = dict(u._STAGES, all=3)
+    with pytest.raises(RuntimeError):
+        u.spmv(x, out)
+    assert torch.equal(out, torch.full_like(out, -7.0))
+    del u._STAGES
+    # the C entry points name the same sets: PCMX_ERR_ARG before any pointer is read (none is valid here)
+    import ctypes
+    import re
+    from pathlib import Path
+
+    from parallel_c_programs_amd._native import hip_lib
+
+    header = Path(__file__).resolve().parents[1] / "csrc" / "include" / "pcmx_errors.h"
+    err_arg = int(re.search(r"PCMX_ERR_ARG\s*=\s*(-?\d+)", header.read_text()).group(1))
+    lib = hip_lib()
+    colbase = (ctypes.c_int * 16)()
+    good = dict(item_nnz=1024, stage=0, ballot=0, blocks=0, lo=0, n=0, colbase=None)
+    for kw in (dict(item_nnz=0), dict(item_nnz=768), dict(item_nnz=256), dict(item_nnz=384), dict(stage=-1),
+               dict(stage=3), dict(ballot=2), dict(blocks=-1), dict(blocks=256), dict(lo=-1), dict(n=-1),
+               dict(item_nnz=128, colbase=colbase)):
+        a = dict(good, **kw)
+        rc = lib.pcmx_spmv_sliced(*[None] * 7, 2000, 2000, 16, *[None] * 7, 0, a["item_nnz"], a["stage"], a["ballot"],
+                                  a["blocks"], a["lo"], a["n"], a["colbase"], None)
+        assert rc == err_arg, kw
+    for item_nnz, blocks in ((0, 0), (64, 0), (1024, 256), (512, -1)):
+        rc = lib.pcmx_spmv_sliced_pair(None, 2000, item_nnz, blocks, *[None] * 5, 16, *[None] * 4, 0, 1, *[None] * 5,
+                                       16, *[None] * 4, 0, 1, None)
+        assert rc == err_arg, (item_nnz, blocks)
+    assert torch.equal(u.spmv(x, out), ref_u)  # and the matrix still multiplies
 
 
 @pytest.mark.parametrize("item_nnz", [512, 1024])
