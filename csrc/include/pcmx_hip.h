@@ -150,6 +150,37 @@ int pcmx_topk_b32(const void* keys, long long n, long long k, int key_type, int 
 int pcmx_kth_key_b32(const void* keys, long long n, long long k, int key_type, int largest, void* out_dev,
                      void* workspace, unsigned* err_flag, hipStream_t s);
 
+/* ---------------------------------------------------------------- row-wise sort / top-k / k-th value */
+/* The same three operations on every row of a contiguous [rows, cols] matrix of 32-bit keys, one wave or one block per
+ * row (csrc/kernels/rowsort.hip): row r's result equals pcmx_radix_sort / pcmx_topk_b32 / pcmx_kth_key_b32 applied to
+ * keys + r * cols, bit for bit (same transformed keys, stable, F32 keys canonical on output, values moved as bits),
+ * except that PCMX_SORT_INDEX and the top-k indices are int32 positions WITHIN the row. No workspace, no error word, no
+ * communication between blocks, no host sync; the inputs are never written. rows * cols < 2^30.
+ *
+ * pcmx_row_sort_b32: cols <= PCMX_ROWSORT_MAX_COLS. Only the first `keep` (0 <= keep <= cols) entries of each sorted
+ * row are stored: keys_out / vals_out are [rows, keep], so keep = k is the row-wise top-k of a short row. mode is
+ * PCMX_SORT_KEYS / PAIRS / INDEX as for pcmx_radix_sort (keys_out may be NULL in INDEX mode), optionally OR-ed with
+ * PCMX_ROWSORT_WAVE (one wave per row, cols <= PCMX_ROWSORT_WAVE_MAX_COLS) or PCMX_ROWSORT_BLOCK (one 512-thread block
+ * per row) to force a kernel; with neither, rows of at most PCMX_ROWSORT_WAVE_COLS keys take the wave kernel. Rows
+ * start at byte 4 * r * cols, so only the base pointers need alignment: every access is a 4-byte access.
+ * pcmx_row_topk_b32: out_vals / out_idx are [rows, k], the k survivors of each row in ascending position (what
+ * pcmx_topk_b32 gives for sorted == 0); any cols. pcmx_row_sort_b32 in PAIRS mode on them gives the sorted form.
+ * pcmx_row_kth_key_b32: out[r] = the k-th key of row r (1-based, the k-th largest when largest != 0).
+ * All three: a bad key type or mode, sizes out of range (k or keep > cols, rows * cols >= 2^30, cols over the limit), a
+ * NULL or not 16-B aligned base pointer, or an output that overlaps an input or another output: PCMX_ERR_ARG, nothing
+ * launched. rows == 0, cols == 0 or k (keep) == 0: returns 0, nothing launched. */
+#define PCMX_ROWSORT_MAX_COLS 16384
+#define PCMX_ROWSORT_WAVE_MAX_COLS 1024
+#define PCMX_ROWSORT_WAVE_COLS 512
+enum { PCMX_ROWSORT_WAVE = 0x100, PCMX_ROWSORT_BLOCK = 0x200 };
+int pcmx_row_sort_b32(const void* keys_in, void* keys_out, const void* vals_in, void* vals_out, long long rows,
+                      long long cols, long long keep, int key_type, int mode, int descending, int begin_bit, int end_bit,
+                      hipStream_t s);
+int pcmx_row_topk_b32(const void* keys, long long rows, long long cols, long long k, int key_type, int largest,
+                      void* out_vals, void* out_idx, hipStream_t s);
+int pcmx_row_kth_key_b32(const void* keys, long long rows, long long cols, long long k, int key_type, int largest,
+                         void* out, hipStream_t s);
+
 /* ---------------------------------------------------------------- run-length encode / reduce by key */
 /* Collapses runs of equal neighbouring 32-bit keys of a length-n stream and reduces a value stream per run, in one pass
  * on the scan's decoupled look-back plus a small kernel that joins the runs crossing tile borders

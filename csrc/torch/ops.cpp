@@ -430,6 +430,74 @@ at::Tensor kth_value(const at::Tensor& x, int64_t k, bool largest) {
     return out;
 }
 
+// ---------------------------------------------------------------- row-wise sort / top-k / k-th value
+// The same operations on every row of a 2-D [rows, cols] tensor, one wave or one block per row (csrc/kernels/
+// rowsort.hip): no workspace, no error word, no host synchronisation. Sizes, modes and routes are checked by the C entry
+// points (PCMX_ERR_ARG raises here); contiguous 16-B aligned inputs (copied when they are not), fresh outputs.
+at::Tensor row_input(const at::Tensor& x, const char* what) {
+    sort_key_type(x, what);
+    TORCH_CHECK(x.dim() == 2, what, ": expected a 2-D [rows, cols] tensor, got ", x.dim(), " dimensions");
+    return aligned_contig(x);
+}
+
+// (sorted keys [rows, keep], values or int32 positions [rows, keep]); mode: PCMX_SORT_* | PCMX_ROWSORT_* (a forced
+// kernel); with want_keys false (INDEX mode) the first tensor is empty and no keys are written
+std::tuple<at::Tensor, at::Tensor> row_sort(const at::Tensor& keys, const c10::optional<at::Tensor>& values, int64_t keep,
+                                            int64_t mode, bool descending, int64_t begin_bit, int64_t end_bit,
+                                            bool want_keys) {
+    const int key_type = sort_key_type(keys, "row_sort");
+    const at::DeviceGuard g(keys.device());
+    at::Tensor kc = row_input(keys, "row_sort"), vc;
+    const int64_t rows = kc.size(0), cols = kc.size(1), base_mode = mode & 0xff;
+    TORCH_CHECK(keep >= 0, "row_sort: keep = ", keep);
+    if (values.has_value()) {
+        TORCH_CHECK(values->device() == keys.device(), "row_sort: values must be on the keys' device");
+        TORCH_CHECK(values->scalar_type() == at::kFloat || values->scalar_type() == at::kInt, "row_sort: values have dtype ",
+                    values->scalar_type(), ", expected float32 or int32");
+        TORCH_CHECK(values->sizes() == keys.sizes(), "row_sort: values must have the shape of keys");
+        vc = aligned_contig(*values);
+    }
+    TORCH_CHECK(values.has_value() == (base_mode == PCMX_SORT_PAIRS), "row_sort: values go with PCMX_SORT_PAIRS and only with it");
+    at::Tensor ko = at::empty({want_keys ? rows : 0, want_keys ? keep : 0}, keys.options()), vo;
+    if (base_mode == PCMX_SORT_PAIRS) vo = at::empty({rows, keep}, values->options());
+    else if (base_mode == PCMX_SORT_INDEX) vo = at::empty({rows, keep}, keys.options().dtype(at::kInt));
+    else vo = at::empty({0, 0}, keys.options().dtype(at::kInt));
+    if (keep <= cols && (rows == 0 || cols == 0 || keep == 0)) return {ko, vo};  // empty tensors have no base pointer
+    check_rc(pcmx_row_sort_b32(kc.data_ptr(), want_keys ? ko.data_ptr() : nullptr, values.has_value() ? vc.data_ptr() : nullptr,
+                               base_mode == PCMX_SORT_KEYS ? nullptr : vo.data_ptr(), rows, cols, keep, key_type, (int)mode,
+                               descending ? 1 : 0, (int)begin_bit, (int)end_bit, cur_stream(keys)),
+             "row_sort");
+    return {ko, vo};
+}
+
+// the k survivors of every row in ascending position: (canonical values [rows, k], int32 positions [rows, k])
+std::tuple<at::Tensor, at::Tensor> row_topk(const at::Tensor& x, int64_t k, bool largest) {
+    const int key_type = sort_key_type(x, "row_topk");
+    const at::DeviceGuard g(x.device());
+    at::Tensor xc = row_input(x, "row_topk");
+    TORCH_CHECK(k >= 0, "row_topk: k = ", k);
+    at::Tensor vals = at::empty({xc.size(0), k}, x.options()), idx = at::empty({xc.size(0), k}, x.options().dtype(at::kInt));
+    if (k <= xc.size(1) && (xc.numel() == 0 || k == 0)) return {vals, idx};  // empty tensors have no base pointer
+    check_rc(pcmx_row_topk_b32(xc.data_ptr(), xc.size(0), xc.size(1), k, key_type, largest ? 1 : 0, vals.data_ptr(),
+                               idx.data_ptr(), cur_stream(x)),
+             "row_topk");
+    return {vals, idx};
+}
+
+// the k-th key (1-based) of every row, [rows]
+at::Tensor row_kth(const at::Tensor& x, int64_t k, bool largest) {
+    const int key_type = sort_key_type(x, "row_kth");
+    const at::DeviceGuard g(x.device());
+    at::Tensor xc = row_input(x, "row_kth");
+    TORCH_CHECK(k >= 1, "row_kth: k = ", k);
+    at::Tensor out = at::empty({xc.size(0)}, x.options());
+    if (xc.size(0) == 0) return out;
+    check_rc(pcmx_row_kth_key_b32(xc.data_ptr(), xc.size(0), xc.size(1), k, key_type, largest ? 1 : 0, out.data_ptr(),
+                                  cur_stream(x)),
+             "row_kth");
+    return out;
+}
+
 // ---------------------------------------------------------------- run-length encode / reduce by key
 // Runs of equal neighbouring keys (compared as bit patterns) of the flattened input, one pass on the scan's look-back
 // (csrc/kernels/segreduce.hip). Like the select ops: per-run outputs have room for keys.numel() entries, the run count
@@ -1358,6 +1426,9 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("sort_index(Tensor keys, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor)");
     m.def("topk(Tensor x, int k, bool largest=True, bool sorted=True) -> (Tensor, Tensor)");
     m.def("kth_value(Tensor x, int k, bool largest=False) -> Tensor");
+    m.def("row_sort(Tensor keys, Tensor? values, int keep, int mode, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor)");
+    m.def("row_topk(Tensor x, int k, bool largest=True) -> (Tensor, Tensor)");
+    m.def("row_kth(Tensor x, int k, bool largest=False) -> Tensor");
     m.def("run_length_encode(Tensor keys, bool starts=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_counts=None, Tensor(c!)? out_starts=None) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("reduce_by_key(Tensor keys, Tensor values, int op, Tensor(a!)? out_keys=None, Tensor(b!)? out=None) -> (Tensor, Tensor, Tensor)");
     m.def("scan_by_key(Tensor keys, Tensor values, int op, bool exclusive=False, Tensor(a!)? out=None) -> Tensor");
@@ -1416,6 +1487,9 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("sort_index", sort_index);
     m.impl("topk", topk);
     m.impl("kth_value", kth_value);
+    m.impl("row_sort", row_sort);
+    m.impl("row_topk", row_topk);
+    m.impl("row_kth", row_kth);
     m.impl("run_length_encode", run_length_encode);
     m.impl("reduce_by_key", reduce_by_key);
     m.impl("scan_by_key", scan_by_key);

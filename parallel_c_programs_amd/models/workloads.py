@@ -1305,10 +1305,95 @@ class Merge(Workload):
                 "check_passed": ok}
 
 
+class RowSort(Workload):
+    """Row-wise sort / top-k / k-th value of a [rows, cols] matrix per GPU along its last dimension
+    (csrc/kernels/rowsort.hip): mode "keys" (ops.sort_keys), "index" (ops.sort), "pairs" (ops.sort_by_key with the keys
+    as their own payload), "topk" (ops.topk with k) or "kth" (ops.kth_value with k); dtype f32 (multiples of 1/64 from
+    a normal distribution, so every row has ties) or i32 (the full range). route is the ops' (None picks by shape).
+    No communication (weak scaling)."""
+
+    MODES = ("keys", "index", "pairs", "topk", "kth")
+
+    def __init__(self, ctx, rows=1 << 14, cols=4096, k=64, mode="keys", dtype="f32", descending=False, route=None, **_):
+        if mode not in self.MODES:
+            raise ValueError(f"rowsort mode {mode!r}: one of {self.MODES}")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"rowsort dtype {dtype!r}: f32 or i32")
+        rows, cols, k = int(rows), int(cols), int(k)
+        if mode in ("topk", "kth") and not (1 if mode == "kth" else 0) <= k <= cols:
+            raise ValueError(f"rowsort k {k}: at most cols = {cols}")
+        super().__init__(ctx, {"rows": rows, "cols": cols, "k": k, "mode": mode, "dtype": dtype,
+                               "descending": bool(descending), "route": route}, "rowsort", "GB/s")
+        self.mode, self.k, self.descending, self.route = mode, k, bool(descending), route
+        g = torch.Generator(device=ctx.device).manual_seed(16000 + ctx.rank)
+        if dtype == "f32":
+            self.x = torch.round(torch.randn(rows, cols, device=ctx.device, generator=g) * 64) / 64
+        else:
+            self.x = torch.randint(-(1 << 31), 1 << 31, (rows, cols), device=ctx.device, generator=g,
+                                   dtype=torch.int64).to(torch.int32)
+        self.out = None
+
+    def step(self):
+        x, d, r = self.x, self.descending, self.route
+        if self.mode == "keys":
+            self.out = (ops.sort_keys(x, d, dim=-1, route=r),)
+        elif self.mode == "index":
+            self.out = ops.sort(x, d, dim=-1, route=r)
+        elif self.mode == "pairs":
+            self.out = ops.sort_by_key(x, x, d, dim=-1, route=r)
+        elif self.mode == "topk":
+            self.out = ops.topk(x, self.k, largest=d, dim=-1, route=r)
+        else:
+            self.out = (ops.kth_value(x, self.k, largest=d, dim=-1),)
+
+    def torch_step(self):
+        """The torch call this replaces (the vendor bar)."""
+        if self.mode == "topk":
+            return torch.topk(self.x, self.k, dim=-1, largest=self.descending)
+        if self.mode == "kth":
+            return torch.kthvalue(self.x, self.k if not self.descending else self.x.shape[1] - self.k + 1, dim=-1)
+        return torch.sort(self.x, dim=-1, stable=True, descending=self.descending)
+
+    def work_per_step(self):
+        # the bytes a caller sees move: the keys read once, and what is written
+        n, kept = self.x.numel(), self.x.shape[0] * self.k
+        return float({"keys": 8 * n, "index": 12 * n, "pairs": 16 * n, "topk": 4 * n + 8 * kept,
+                      "kth": 4 * n + 4 * self.x.shape[0]}[self.mode])
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gkeys_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        return rep
+
+    def check(self, reduce: bool = True):
+        """The outputs of the timed step against torch.sort(dim=-1, stable=True) of a host copy, exactly (values bit
+        for bit: the generated keys hold no NaN; a -0.0 comes out as +0.0 on both sides). Local only."""
+        xh = self.x.cpu()
+        ref = torch.sort(xh, dim=-1, stable=True, descending=self.descending)
+        rv = torch.where(ref.values == 0, torch.zeros_like(ref.values), ref.values)
+        ri = ref.indices.int()
+        out = [t.cpu() for t in self.out]
+        same = lambda a, b: a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+        if self.mode == "keys":
+            ok = same(out[0], rv)
+        elif self.mode == "index":
+            ok = same(out[0], rv) and same(out[1], ri)
+        elif self.mode == "pairs":
+            ok = same(out[0], rv) and same(out[1], torch.gather(xh.view(torch.int32), 1, ref.indices).view(xh.dtype))
+        elif self.mode == "topk":
+            ok = same(out[0], rv[:, :self.k]) and same(out[1], ri[:, :self.k])
+        else:
+            ok = same(out[0], rv[:, self.k - 1])
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"elements_checked": self.x.numel(), "exact_vs_torch": ok, "check_passed": ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
              "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
-             "merge": Merge}
+             "merge": Merge, "rowsort": RowSort}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

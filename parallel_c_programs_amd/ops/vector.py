@@ -274,8 +274,13 @@ def _canonical_f32(v: torch.Tensor) -> torch.Tensor:
     return torch.where(torch.isnan(v), torch.full_like(v.view(torch.int32), _NAN_BITS).view(torch.float32), v)
 
 
-def sort_keys(x: torch.Tensor, descending: bool = False, bits: int | None = None) -> torch.Tensor:
-    """The sorted values of x.flatten() (float32 or int32), 1-D. float32 zeros and NaNs come out canonical (above)."""
+def sort_keys(x: torch.Tensor, descending: bool = False, bits: int | None = None, dim: int | None = None,
+              route: str | None = None) -> torch.Tensor:
+    """The sorted values of x.flatten() (float32 or int32), 1-D. float32 zeros and NaNs come out canonical (above).
+    dim=int: every row along dim is sorted on its own, the result has x's shape (the row-wise section below)."""
+    if dim is not None:
+        return _row_sort(x, None, "keys", descending, bits, dim, route)[0]
+    _no_route(route)
     nbits = _check_sort_keys(x, bits)
     if x.is_cuda:
         return ops().sort_keys(x, bool(descending), 0, nbits)
@@ -283,9 +288,14 @@ def sort_keys(x: torch.Tensor, descending: bool = False, bits: int | None = None
     return _canonical_f32(xf[_host_order(xf, bool(descending), nbits)])
 
 
-def sort(x: torch.Tensor, descending: bool = False, bits: int | None = None):
+def sort(x: torch.Tensor, descending: bool = False, bits: int | None = None, dim: int | None = None,
+         route: str | None = None):
     """(values, indices) of the stable sort of x.flatten(): torch.sort(x.flatten(), stable=True) with int32 indices.
-    On float32 this is slower than torch on an MI355X (2^28 keys: 10.16 ms against 9.73 ms; faster on int32)."""
+    On float32 this is slower than torch on an MI355X (2^28 keys: 10.16 ms against 9.73 ms; faster on int32).
+    dim=int: torch.sort(x, dim, stable=True) with int32 positions along dim (the row-wise section below)."""
+    if dim is not None:
+        return _row_sort(x, None, "index", descending, bits, dim, route)
+    _no_route(route)
     nbits = _check_sort_keys(x, bits)
     if x.is_cuda:
         return tuple(ops().sort_index(x, bool(descending), 0, nbits, True))
@@ -294,16 +304,26 @@ def sort(x: torch.Tensor, descending: bool = False, bits: int | None = None):
     return _canonical_f32(xf[order]), order.int()
 
 
-def argsort(x: torch.Tensor, descending: bool = False, bits: int | None = None) -> torch.Tensor:
-    """The int32 indices of the stable sort of x.flatten(); no sorted-keys tensor is written."""
+def argsort(x: torch.Tensor, descending: bool = False, bits: int | None = None, dim: int | None = None,
+            route: str | None = None) -> torch.Tensor:
+    """The int32 indices of the stable sort of x.flatten(); no sorted-keys tensor is written. dim=int: the int32
+    positions along dim of every row's stable sort, x's shape (the row-wise section below)."""
+    if dim is not None:
+        return _row_sort(x, None, "argsort", descending, bits, dim, route)[1]
+    _no_route(route)
     nbits = _check_sort_keys(x, bits)
     if x.is_cuda:
         return ops().sort_index(x, bool(descending), 0, nbits, False)[1]
     return _host_order(x.reshape(-1), bool(descending), nbits).int()
 
 
-def sort_by_key(keys: torch.Tensor, values: torch.Tensor, descending: bool = False, bits: int | None = None):
-    """(keys_sorted, values_sorted): values (float32 or int32, same numel, moved as bits) reordered with their keys."""
+def sort_by_key(keys: torch.Tensor, values: torch.Tensor, descending: bool = False, bits: int | None = None,
+                dim: int | None = None, route: str | None = None):
+    """(keys_sorted, values_sorted): values (float32 or int32, same numel, moved as bits) reordered with their keys.
+    dim=int: row by row along dim; values must then have the shape of keys (the row-wise section below)."""
+    if dim is not None:
+        return _row_sort(keys, values, "pairs", descending, bits, dim, route)
+    _no_route(route)
     nbits = _check_sort_keys(keys, bits, "keys")
     if values.dtype not in (torch.float32, torch.int32):
         raise TypeError(f"values must be float32 or int32, got {values.dtype}")
@@ -360,7 +380,8 @@ def _check_topk(x: torch.Tensor, k, k_min: int, name: str) -> None:
         raise ValueError(f"{name}: k must be in {k_min}..{x.numel()} (the number of elements), got {k}")
 
 
-def topk(x: torch.Tensor, k: int, largest: bool = True, sorted: bool = True, method: str | None = None):
+def topk(x: torch.Tensor, k: int, largest: bool = True, sorted: bool = True, method: str | None = None,
+         dim: int | None = None, route: str | None = None):
     """(values, indices): the k largest (or smallest) elements of x.flatten() (float32 or int32, at most SORT_MAX_N
     elements, never written) and their int32 flat indices; exactly the first k entries of sort(x, descending=largest).
     Stricter than torch.topk, which leaves the choice among ties open: elements that tie with the k-th key are taken by
@@ -372,7 +393,13 @@ def topk(x: torch.Tensor, k: int, largest: bool = True, sorted: bool = True, met
     numel, 11.14 against 10.09 ms), select otherwise. At 2^28 keys select is 4.1x-13.4x faster than torch.topk for k <=
     2^24 (f32 k = 1024: 1.53 against 9.72 ms) and 1.26x-2.0x at numel / 2; method="select" with sorted=True on float32
     is slower than torch.topk from k = 7/8 numel (11.14 against 10.86 ms; 12.72 against 11.03 ms at k = numel), where
-    the default rule takes the sort route (10.09 ms)."""
+    the default rule takes the sort route (10.09 ms). dim=int: the top-k of every row along dim, shape of x with dim
+    replaced by k, int32 positions along dim; method is for dim=None, route for dim=int (the row-wise section below)."""
+    if dim is not None:
+        if method is not None:
+            raise ValueError("topk: method is for dim=None; with dim use route")
+        return _row_topk(x, k, largest, sorted, dim, route)
+    _no_route(route)
     _check_topk(x, k, 0, "topk")
     if method not in _TOPK_METHODS:
         raise ValueError(f"topk: method must be one of {_TOPK_METHODS}, got {method!r}")
@@ -393,15 +420,248 @@ def topk(x: torch.Tensor, k: int, largest: bool = True, sorted: bool = True, met
     return v, i
 
 
-def kth_value(x: torch.Tensor, k: int, largest: bool = False) -> torch.Tensor:
+def kth_value(x: torch.Tensor, k: int, largest: bool = False, dim: int | None = None) -> torch.Tensor:
     """The k-th smallest (largest=True: k-th largest) element of x.flatten() as a 0-d tensor on x's device: 1-based
     like torch.kthvalue, equal to sort_keys(x, descending=largest)[k - 1] (float32 canonical). On the GPU the
-    threshold of the radix-select passes alone: four read passes, nothing moved, no host synchronisation."""
+    threshold of the radix-select passes alone: four read passes, nothing moved, no host synchronisation. dim=int: the
+    k-th value of every row along dim, shape of x without dim (the row-wise section below)."""
+    if dim is not None:
+        return _row_kth(x, k, largest, dim)
     _check_topk(x, k, 1, "kth_value")
     if x.is_cuda:
         return ops().kth_value(x, k, bool(largest))
     xf = x.reshape(-1)
     return _canonical_f32(xf[torch.sort(xf, stable=True, descending=bool(largest)).indices[k - 1:k]]).reshape(())
+
+
+# ---------------------------------------------------------------- row-wise sort / top-k / k-th value (dim=)
+# sort_keys, sort, argsort, sort_by_key, topk and kth_value with dim=int work on every row along dim on its own, with
+# torch's output shapes, and are DEFINED by the 1-D ops above: every row's result equals the 1-D op applied to that row,
+# bit for bit (same key order, stable, float32 keys canonical, payloads moved as bits). Indices are int32 positions
+# along dim. A dim that is not the last is moved last and made contiguous, and the result is moved back, as torch
+# does. On the GPU rows of up to ROWSORT_MAX_COLS keys are sorted inside one wave or one block per row
+# (csrc/kernels/rowsort.hip; no counterpart in the reference programs): no workspace, no look-back, nothing that could
+# time out, so scan_check() has nothing to report for them. Nothing synchronises with the host.
+#  * route (tests and the lab) forces a GPU route and raises ValueError when it cannot take the shape; it is validated
+#    on CPU tensors too, which otherwise ignore it. Sort routes: "wave" (one wave per row, cols <=
+#    ROWSORT_WAVE_MAX_COLS), "block" (one 512-thread block per row, cols <= ROWSORT_MAX_COLS), "loop" (the 1-D sort per
+#    row) and "global" (one 1-D stable index sort of all keys, then a stable sort by row id with bits = ceil(log2 rows):
+#    any row length at about twice a flat sort). Top-k routes: "sortkeep" (the row sort storing only the first k
+#    columns, cols <= ROWSORT_MAX_COLS), "select" (one block per row: four histogram passes and one ordered sweep, then
+#    the row sort of the [rows, k] survivors) and "loop" (the 1-D topk per row). kth_value is the select kernel's
+#    histogram passes alone.
+#  * route=None picks by the constants below, each set from the lab's A/B of the two routes it separates on one MI355X
+#    (scripts/rowsort_lab.py, profiles/r16_rowsort/README.md; float32, median ms of 5 interleaved runs):
+#    - ROWSORT_WAVE_COLS: 2^24 keys, keys + indices: wave against block 0.152 / 0.203 at cols = 512, 0.184 / 0.167 at
+#      1024 (keys alone 0.147 / 0.197 and 0.157 / 0.160); wave is 2.2x-5.4x faster from 256 down to 32.
+#    - ROWSORT_LOOP_MIN_COLS: the border is in cols, not in rows: the loop pays launches per row, "global" pays the
+#      row-id passes per key. Loop against global, keys + indices, rows = 2 / 8: 0.523 / 0.435 and 2.096 / 0.669 at
+#      cols = 2^20; 0.632 / 0.663 and 2.524 / 2.230 at 2^22; 0.833 / 1.122 and 3.362 / 4.335 at 2^23. At 2^22 the loop
+#      wins three of the four measured cases (keys alone 0.448 / 0.525 and 1.745 / 1.840) and loses [8, 2^22] with
+#      indices by 12%; at 32768-key rows "global" wins from two rows (0.282 / 0.228) to 64 (9.306 / 0.474). One row is
+#      the loop: the same work.
+#    - ROW_TOPK_SORT_FRACTION: select against sortkeep at [8192, 2048]: 0.136 / 0.143 at k = cols / 8, 0.152 / 0.143 at
+#      cols / 4, 0.190 / 0.145 at cols / 2; at [1024, 16384]: 0.159 / 0.238 at cols / 4, 0.246 / 0.244 at cols / 2,
+#      0.360 / 0.245 at 3/4 cols. k = cols / 4 itself is select: 6% slower than sortkeep at cols = 2048, 1.5x faster at
+#      16384.
+#    - ROW_TOPK_LOOP_COLS_PER_ROW: the select kernel puts one block on a row and takes about 3.1 ns per key of a row
+#      whatever the number of rows (up to the CUs); the loop takes about 0.12 ms per row. Select against loop, k = 64:
+#      one row 0.097 / 0.123 at cols = 32768, 0.336 / 0.125 at 131072; eight rows 0.344 / 0.925 at 131072 (16384 per
+#      row), 1.308 / 1.026 at 524288 (65536 per row).
+#  * Measured against torch on one MI355X (profiles/r16_rowsort/README.md): sort 2.6x-3.2x faster than torch.sort(dim=-1,
+#    stable=True) for rows of 32 to 16384 keys with indices (1.9x at [16384, 4096]); top-k 1.5x-2.1x faster than
+#    torch.topk at [4096, 4096] and [65536, 512], 1.02x-1.10x at [512, 131072]. SLOWER than torch: the "global" sort
+#    route ([1024, 32768]: 2.29 ms keys, 3.17 ms with indices against 1.64 ms, 0.52x-0.77x), float32 sort with indices
+#    of [8, 2^24] by the loop (5.92 against 4.43 ms, 0.75x; keys alone 1.06x, int32 1.07x-1.65x), top-k of one row of
+#    131072 keys for k >= 8 (0.13 against 0.07 ms, 0.53x-0.57x; k = 1 1.2x) and of [64, 32768] (0.095-0.118 against
+#    0.089-0.110 ms on the minimum of 5, 0.85x-0.95x).
+ROWSORT_MAX_COLS = 16384       # csrc/include/pcmx_hip.h PCMX_ROWSORT_MAX_COLS: sort.hip's tile, one block's LDS
+ROWSORT_WAVE_MAX_COLS = 1024   # PCMX_ROWSORT_WAVE_MAX_COLS: 16 keys per lane
+ROWSORT_WAVE_COLS = 512        # W: rows up to here take the wave kernel, longer ones the block kernel
+ROWSORT_LOOP_MIN_COLS = 1 << 22  # rows longer than ROWSORT_MAX_COLS: "loop" from this many keys per row (or one row)
+ROW_TOPK_SORT_FRACTION = 0.25  # cols <= ROWSORT_MAX_COLS: "sortkeep" when k > this * cols, "select" otherwise
+ROW_TOPK_LOOP_COLS_PER_ROW = 65536  # "loop" (the device-wide topk per row) when cols >= this * rows
+_ROW_SORT_ROUTES = (None, "wave", "block", "loop", "global")
+_ROW_TOPK_ROUTES = (None, "sortkeep", "select", "loop")
+_MODE_KEYS, _MODE_PAIRS, _MODE_INDEX = 0, 1, 2          # PCMX_SORT_*
+_ROUTE_FLAG = {"wave": 0x100, "block": 0x200}           # PCMX_ROWSORT_WAVE / PCMX_ROWSORT_BLOCK
+
+
+def _no_route(route) -> None:
+    if route is not None:
+        raise ValueError("route selects a row-wise kernel: it needs dim")
+
+
+def _rows_of(x: torch.Tensor, dim, name: str):
+    """(x as contiguous [rows, cols] with dim last, the dim-last shape, dim normalised)."""
+    if isinstance(dim, bool) or not isinstance(dim, int):
+        raise TypeError(f"{name}: dim must be an int or None, got {type(dim).__name__}")
+    if x.dim() < 1 or not -x.dim() <= dim < x.dim():
+        raise IndexError(f"{name}: dim {dim} is out of range for a tensor with {x.dim()} dimensions")
+    d = dim % x.dim()
+    xm = x.movedim(d, -1)
+    cols = xm.shape[-1]
+    rows = xm.numel() // cols if cols else int(torch.Size(xm.shape[:-1]).numel())
+    return xm.reshape(rows, cols).contiguous(), tuple(xm.shape), d
+
+
+def _rows_back(t: torch.Tensor, shape, d: int) -> torch.Tensor:
+    return t.reshape(*shape[:-1], t.shape[-1]).movedim(-1, d)
+
+
+def _sort_route(route, rows: int, cols: int, name: str) -> str:
+    if route not in _ROW_SORT_ROUTES:
+        raise ValueError(f"{name}: route must be one of {_ROW_SORT_ROUTES}, got {route!r}")
+    if route is None:
+        if cols <= ROWSORT_WAVE_COLS:
+            return "wave"
+        if cols <= ROWSORT_MAX_COLS:
+            return "block"
+        return "loop" if rows == 1 or cols >= ROWSORT_LOOP_MIN_COLS else "global"
+    limit = {"wave": ROWSORT_WAVE_MAX_COLS, "block": ROWSORT_MAX_COLS}.get(route)
+    if limit is not None and cols > limit:
+        raise ValueError(f"{name}: route {route!r} takes rows of at most {limit} keys, got {cols}")
+    return route
+
+
+def _gather_bits(src2: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
+    """src2[r, order[r, j]] moved as bits (a float gather would be free to quieten a signalling NaN payload)."""
+    return torch.gather(src2.view(torch.int32), 1, order.long()).view(src2.dtype)
+
+
+def _row_sort_global(k2: torch.Tensor, v2, descending: bool, nbits: int, want_keys: bool, want_pos: bool):
+    """(sorted keys, int32 positions, sorted values), each None when not wanted, of every row of k2 with the device-wide
+    kernels: one stable index sort of all keys, then a stable pair sort by row id per wanted stream: keys of one row
+    stay in their sorted order."""
+    rows, cols = k2.shape
+    want_pos = want_pos or v2 is not None
+    ks, fi = ops().sort_index(k2.reshape(-1), descending, 0, nbits, True)
+    if rows > 1:
+        rid = torch.div(fi, cols, rounding_mode="floor")
+        rbits = (rows - 1).bit_length()
+        if want_keys:
+            ks = ops().sort_pairs(rid, ks, False, 0, rbits)[1]
+        if want_pos:
+            fi = ops().sort_pairs(rid, fi, False, 0, rbits)[1]
+    pos = None
+    if want_pos:
+        pos = fi.view(rows, cols) - (torch.arange(rows, device=k2.device, dtype=torch.int32) * cols)[:, None]
+    vs = None if v2 is None else _gather_bits(v2, pos)
+    return (ks.view(rows, cols) if want_keys else None), pos, vs
+
+
+def _row_sort_gpu(k2: torch.Tensor, v2, mode: str, keep: int, descending: bool, nbits: int, route: str):
+    """(keys or None, payload or None), each [rows, keep], of the row sort of k2 on the GPU by `route`."""
+    rows, cols = k2.shape
+    want_keys = mode != "argsort"
+    if route in _ROUTE_FLAG:
+        code = {"keys": _MODE_KEYS, "pairs": _MODE_PAIRS}.get(mode, _MODE_INDEX) | _ROUTE_FLAG[route]
+        ko, vo = ops().row_sort(k2, v2, keep, code, descending, 0, nbits, want_keys)
+        return (ko if want_keys else None), (None if mode == "keys" else vo)
+    if route == "global":
+        ks, pos, vs = _row_sort_global(k2, v2, descending, nbits, want_keys, mode not in ("keys", "pairs"))
+    else:  # "loop": the device-wide sort, row by row
+        ks = pos = vs = None
+        if mode == "keys":
+            ks = torch.stack([ops().sort_keys(r, descending, 0, nbits) for r in k2])
+        elif mode == "pairs":
+            ks, vs = (torch.stack(t) for t in zip(*(ops().sort_pairs(r, v, descending, 0, nbits) for r, v in zip(k2, v2))))
+        else:
+            ks, pos = (torch.stack(t) for t in zip(*(ops().sort_index(r, descending, 0, nbits, True) for r in k2)))
+    payload = vs if mode == "pairs" else pos
+    return (ks[:, :keep] if want_keys else None), (None if mode == "keys" else payload[:, :keep])
+
+
+def _row_sort(keys: torch.Tensor, values, mode: str, descending, bits, dim, route):
+    """The row-wise form of sort_keys / sort / argsort / sort_by_key: (keys or None, payload or None) in x's shape."""
+    nbits = _check_sort_keys(keys, bits, "keys" if mode == "pairs" else "x")
+    descending = bool(descending)
+    if mode == "pairs":
+        if values.dtype not in (torch.float32, torch.int32):
+            raise TypeError(f"values must be float32 or int32, got {values.dtype}")
+        if values.shape != keys.shape:
+            raise ValueError(f"with dim the values must have the keys' shape {tuple(keys.shape)}, got {tuple(values.shape)}")
+        if values.device != keys.device:
+            raise ValueError(f"values are on {values.device}, the keys on {keys.device}")
+    k2, shape, d = _rows_of(keys, dim, "sort")
+    v2 = _rows_of(values, dim, "sort")[0] if mode == "pairs" else None
+    rows, cols = k2.shape
+    route = _sort_route(route, rows, cols, "sort")
+    if k2.numel() == 0:
+        ko, po = k2.clone(), (v2.clone() if mode == "pairs" else k2.new_empty(k2.shape, dtype=torch.int32))
+    elif keys.is_cuda:
+        ko, po = _row_sort_gpu(k2, v2, mode, cols, descending, nbits, route)
+    else:
+        key = k2 if nbits == 32 else k2.long() & ((1 << nbits) - 1)
+        order = torch.sort(key, dim=-1, stable=True, descending=descending).indices
+        ko = _canonical_f32(_gather_bits(k2, order))
+        po = _gather_bits(v2, order) if mode == "pairs" else order.int()
+    return (None if mode == "argsort" else _rows_back(ko, shape, d)), (None if mode == "keys" else _rows_back(po, shape, d))
+
+
+def _check_row_k(x: torch.Tensor, k, k_min: int, cols: int, name: str) -> None:
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"{name}: k must be an int, got {type(k).__name__}")
+    if not k_min <= k <= cols:
+        raise ValueError(f"{name}: k must be in {k_min}..{cols} (the size of dim), got {k}")
+
+
+def _topk_route(route, rows: int, cols: int, k: int, name: str) -> str:
+    if route not in _ROW_TOPK_ROUTES:
+        raise ValueError(f"{name}: route must be one of {_ROW_TOPK_ROUTES}, got {route!r}")
+    if route is None:
+        if cols >= ROW_TOPK_LOOP_COLS_PER_ROW * rows:
+            return "loop"
+        return "sortkeep" if cols <= ROWSORT_MAX_COLS and k > ROW_TOPK_SORT_FRACTION * cols else "select"
+    if route == "sortkeep" and cols > ROWSORT_MAX_COLS:
+        raise ValueError(f"{name}: route 'sortkeep' takes rows of at most {ROWSORT_MAX_COLS} keys, got {cols}")
+    return route
+
+
+def _small_sort_route(cols: int) -> str:
+    return "wave" if cols <= ROWSORT_WAVE_COLS else ("block" if cols <= ROWSORT_MAX_COLS else "global")
+
+
+def _row_topk(x: torch.Tensor, k, largest, sorted, dim, route):
+    _check_topk(x, 0, 0, "topk")  # dtype and the element limit; k is checked against the size of dim
+    largest = bool(largest)
+    x2, shape, d = _rows_of(x, dim, "topk")
+    rows, cols = x2.shape
+    _check_row_k(x, k, 0, cols, "topk")
+    route = _topk_route(route, rows, cols, k, "topk")
+    if rows == 0 or k == 0:
+        v, i = x2.new_empty((rows, k)), x2.new_empty((rows, k), dtype=torch.int32)
+    elif not x.is_cuda:
+        order = torch.sort(x2, dim=-1, stable=True, descending=largest).indices[:, :k]
+        if not sorted:
+            order = torch.sort(order, dim=-1).values
+        v, i = _canonical_f32(_gather_bits(x2, order)), order.int()
+    elif route == "loop":
+        v, i = (torch.stack(t) for t in zip(*(tuple(ops().topk(r, k, largest, bool(sorted))) for r in x2)))
+    elif route == "sortkeep":
+        v, i = _row_sort_gpu(x2, None, "index", k, largest, 32, _small_sort_route(cols))
+        if not sorted and k > 1:  # back to position order: positions are distinct, the values ride along
+            i, v = _row_sort_gpu(i, v, "pairs", k, False, 32, _small_sort_route(k))
+    else:
+        v, i = ops().row_topk(x2, k, largest)
+        if sorted and k > 1:  # canonical values transform to the same keys again and the sort is stable
+            v, i = _row_sort_gpu(v, i, "pairs", k, largest, 32, _small_sort_route(k))
+    return _rows_back(v, shape, d), _rows_back(i, shape, d)
+
+
+def _row_kth(x: torch.Tensor, k, largest, dim):
+    _check_topk(x, 0, 0, "kth_value")  # dtype and the element limit; k is checked against the size of dim
+    x2, shape, d = _rows_of(x, dim, "kth_value")
+    rows, cols = x2.shape
+    _check_row_k(x, k, 1, cols, "kth_value")
+    if rows == 0:
+        out = x2.new_empty((0,))
+    elif x.is_cuda:
+        out = ops().row_kth(x2, k, bool(largest))
+    else:
+        order = torch.sort(x2, dim=-1, stable=True, descending=bool(largest)).indices[:, k - 1:k]
+        out = _canonical_f32(_gather_bits(x2, order))
+    return out.reshape(shape[:-1])
 
 
 # ---------------------------------------------------------------- run-length encode / reduce by key / unique
