@@ -181,6 +181,51 @@ int pcmx_row_topk_b32(const void* keys, long long rows, long long cols, long lon
 int pcmx_row_kth_key_b32(const void* keys, long long rows, long long cols, long long k, int key_type, int largest,
                          void* out, hipStream_t s);
 
+/* ---------------------------------------------------------------- reduce / scan along a dimension */
+/* op (PCMX_OP_SUM / MIN / MAX) along the middle extent of a contiguous [outer, n, inner] tensor, read where it lies
+ * (csrc/kernels/axis.hip): reduce writes out [outer, inner], scan writes out [outer, n, inner] (exclusive != 0: the
+ * first element along n gets the identity, +0.0 / 0, +inf / INT32_MAX, -inf / INT32_MIN). int32 sums wrap mod 2^32 and
+ * int32 results are exact; float32 min / max are exact and hand on a NaN (a scan: to the end of that row only); a
+ * float32 sum uses the fixed association order written down in axis.hip's header, which depends on n, inner, the route
+ * and the chunk only: the same row gives the same bits wherever it stands and on every call. Rows never mix. No block
+ * waits for another, nothing can time out, there is no err_flag and no host sync; the split routes meet through the
+ * workspace between their two or three launches on the stream.
+ * route: 0 picks by the PCMX_AXIS_* borders below; PCMX_AXIS_GROUP (inner == 1, n <= PCMX_AXIS_GROUP_MAX_N: G lanes
+ * per row), PCMX_AXIS_BLOCK (inner == 1, n <= PCMX_AXIS_BLOCK_MAX_N: one block per row), PCMX_AXIS_SPLIT (inner == 1:
+ * chunks of a row over blocks), PCMX_AXIS_COLUMN (inner > 1: a thread walks down 4 adjacent columns) and
+ * PCMX_AXIS_COLUMN_SPLIT (inner > 1: chunks of n over threads) force a route. chunk: 0 for the default, else the
+ * elements along n per chunk of a split route: a multiple of 1024 for SPLIT, at least PCMX_AXIS_COLUMN_MIN_CHUNK for
+ * COLUMN_SPLIT; non-zero with any other route is refused.
+ * x, out and the workspace 16-B aligned (rows start wherever n and inner put them: only the bases need alignment).
+ * The input is never written, except that a scan's out may be x itself (in place). The workspace
+ * (pcmx_axis_workspace_bytes, one call in flight per workspace) may be NULL for the routes that are not split.
+ * PCMX_ERR_ARG with nothing launched: a NULL or misaligned x or out (a NULL workspace on a split route), an out that
+ * partly overlaps x, an unknown op or route, a route that cannot take the shape, a bad chunk, a negative extent, or
+ * outer * n * inner >= 2^31. Any zero extent returns 0 and launches nothing, except a SUM reduce with n == 0 and
+ * outer * inner > 0, which fills out with zeros. */
+#define PCMX_AXIS_GROUP_MAX_N 4096        /* the group kernel's limit when forced: 16 quads per lane */
+#define PCMX_AXIS_GROUP_N 2048            /* default, reduce: rows up to here take group, longer ones block */
+#define PCMX_AXIS_GROUP_SCAN_N 512        /* default, scan: the same border */
+#define PCMX_AXIS_BLOCK_MAX_N (1 << 20)   /* rows longer than this always take split */
+#define PCMX_AXIS_SPLIT_ROWS 512          /* default: with fewer rows than this ... */
+#define PCMX_AXIS_SPLIT_MIN_N (1 << 17)   /* ... rows from this length take split */
+#define PCMX_AXIS_SPLIT_CHUNK 32768       /* default chunk of split */
+#define PCMX_AXIS_COLUMN_MIN_UNITS 65536  /* default, scan: column when outer * ceil(inner / 4) threads reach this ... */
+#define PCMX_AXIS_COLUMN_MIN_BLOCKS 1024  /* default, reduce: column when outer * (64-quad tiles of inner) reach this ... */
+#define PCMX_AXIS_COLUMN_SPLIT_MIN_N 64   /* ... or n is below this; column_split otherwise */
+#define PCMX_AXIS_COLUMN_REDUCE_BLOCKS 1024 /* the blocks the default chunk of a column_split reduce aims for */
+#define PCMX_AXIS_COLUMN_MIN_CHUNK 16     /* smallest chunk of column_split */
+enum { PCMX_AXIS_GROUP = 1, PCMX_AXIS_BLOCK = 2, PCMX_AXIS_SPLIT = 3, PCMX_AXIS_COLUMN = 4, PCMX_AXIS_COLUMN_SPLIT = 5 };
+long long pcmx_axis_workspace_bytes(long long outer, long long n, long long inner);
+int pcmx_axis_reduce_f32(const float* x, float* out, long long outer, long long n, long long inner, int op, int route,
+                         long long chunk, void* workspace, hipStream_t s);
+int pcmx_axis_reduce_i32(const int32_t* x, int32_t* out, long long outer, long long n, long long inner, int op, int route,
+                         long long chunk, void* workspace, hipStream_t s);
+int pcmx_axis_scan_f32(const float* x, float* out, long long outer, long long n, long long inner, int op, int exclusive,
+                       int route, long long chunk, void* workspace, hipStream_t s);
+int pcmx_axis_scan_i32(const int32_t* x, int32_t* out, long long outer, long long n, long long inner, int op, int exclusive,
+                       int route, long long chunk, void* workspace, hipStream_t s);
+
 /* ---------------------------------------------------------------- run-length encode / reduce by key */
 /* Collapses runs of equal neighbouring 32-bit keys of a length-n stream and reduces a value stream per run, in one pass
  * on the scan's decoupled look-back plus a small kernel that joins the runs crossing tile borders

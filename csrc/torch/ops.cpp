@@ -498,6 +498,71 @@ at::Tensor row_kth(const at::Tensor& x, int64_t k, bool largest) {
     return out;
 }
 
+// ---------------------------------------------------------------- reduce / scan along a dimension
+// x is the contiguous [outer, n, inner] view of the caller's tensor (csrc/kernels/axis.hip). Shapes, op, route and chunk
+// are checked by the C entry points (PCMX_ERR_ARG raises here); the workspace comes from torch's allocator on the
+// current stream; no error word, no host synchronisation.
+at::Tensor axis_input(const at::Tensor& x, const char* what) {
+    TORCH_CHECK(x.is_cuda(), what, ": GPU tensor expected");
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kInt, what, ": x has dtype ", x.scalar_type(),
+                ", expected float32 or int32");
+    TORCH_CHECK(x.dim() == 3, what, ": expected a 3-D [outer, n, inner] tensor, got ", x.dim(), " dimensions");
+    return aligned_contig(x);
+}
+
+// [outer, inner]
+at::Tensor axis_reduce(const at::Tensor& x, int64_t op, int64_t route, int64_t chunk) {
+    const at::DeviceGuard g(x.device());
+    at::Tensor xc = axis_input(x, "axis_reduce");
+    const int64_t outer = xc.size(0), n = xc.size(1), inner = xc.size(2);
+    TORCH_CHECK(n > 0 || op == PCMX_OP_SUM, "axis_reduce: min / max of an empty dimension");
+    if (n == 0) return at::zeros({outer, inner}, x.options());  // (an empty input has no base pointer)
+    at::Tensor out = at::empty({outer, inner}, x.options());
+    if (out.numel() == 0) return out;
+    auto ws = workspace(x, pcmx_axis_workspace_bytes(outer, n, inner));
+    if (x.scalar_type() == at::kFloat)
+        check_rc(pcmx_axis_reduce_f32(xc.data_ptr<float>(), out.data_ptr<float>(), outer, n, inner, (int)op, (int)route, chunk,
+                                      ws.data_ptr(), cur_stream(x)),
+                 "axis_reduce");
+    else
+        check_rc(pcmx_axis_reduce_i32(xc.data_ptr<int32_t>(), out.data_ptr<int32_t>(), outer, n, inner, (int)op, (int)route,
+                                      chunk, ws.data_ptr(), cur_stream(x)),
+                 "axis_reduce");
+    return out;
+}
+
+// [outer, n, inner]; out (contiguous, same numel and dtype) may be x itself
+at::Tensor axis_scan(const at::Tensor& x, int64_t op, bool exclusive, int64_t route, int64_t chunk,
+                     const c10::optional<at::Tensor>& out) {
+    const at::DeviceGuard g(x.device());
+    at::Tensor xc = axis_input(x, "axis_scan");
+    const int64_t outer = xc.size(0), n = xc.size(1), inner = xc.size(2), total = xc.numel();
+    const bool has_out = out.has_value() && out->defined();
+    if (has_out) {
+        check_gpu(*out, "out", x.scalar_type());
+        TORCH_CHECK(out->device() == x.device() && out->is_contiguous() && out->numel() == total,
+                    "axis_scan: out must be contiguous, on x's device, with ", total, " elements");
+    }
+    if (total == 0) return has_out ? *out : at::empty_like(xc);
+    at::Tensor dest = has_out && !(reinterpret_cast<uintptr_t>(out->data_ptr()) & 15u) ? out->view({outer, n, inner})
+                                                                                      : at::empty({outer, n, inner}, x.options());
+    if (overlaps(xc, dest) && xc.data_ptr() != dest.data_ptr()) xc = xc.clone();  // identical is fine: the call is in place
+    auto ws = workspace(x, pcmx_axis_workspace_bytes(outer, n, inner));
+    if (x.scalar_type() == at::kFloat)
+        check_rc(pcmx_axis_scan_f32(xc.data_ptr<float>(), dest.data_ptr<float>(), outer, n, inner, (int)op, exclusive ? 1 : 0,
+                                    (int)route, chunk, ws.data_ptr(), cur_stream(x)),
+                 "axis_scan");
+    else
+        check_rc(pcmx_axis_scan_i32(xc.data_ptr<int32_t>(), dest.data_ptr<int32_t>(), outer, n, inner, (int)op,
+                                    exclusive ? 1 : 0, (int)route, chunk, ws.data_ptr(), cur_stream(x)),
+                 "axis_scan");
+    if (has_out) {
+        if (dest.data_ptr() != out->data_ptr()) out->view(-1).copy_(dest.view(-1));
+        return *out;
+    }
+    return dest;
+}
+
 // ---------------------------------------------------------------- run-length encode / reduce by key
 // Runs of equal neighbouring keys (compared as bit patterns) of the flattened input, one pass on the scan's look-back
 // (csrc/kernels/segreduce.hip). Like the select ops: per-run outputs have room for keys.numel() entries, the run count
@@ -1429,6 +1494,8 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("row_sort(Tensor keys, Tensor? values, int keep, int mode, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor)");
     m.def("row_topk(Tensor x, int k, bool largest=True) -> (Tensor, Tensor)");
     m.def("row_kth(Tensor x, int k, bool largest=False) -> Tensor");
+    m.def("axis_reduce(Tensor x, int op, int route=0, int chunk=0) -> Tensor");
+    m.def("axis_scan(Tensor x, int op, bool exclusive=False, int route=0, int chunk=0, Tensor(a!)? out=None) -> Tensor");
     m.def("run_length_encode(Tensor keys, bool starts=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_counts=None, Tensor(c!)? out_starts=None) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("reduce_by_key(Tensor keys, Tensor values, int op, Tensor(a!)? out_keys=None, Tensor(b!)? out=None) -> (Tensor, Tensor, Tensor)");
     m.def("scan_by_key(Tensor keys, Tensor values, int op, bool exclusive=False, Tensor(a!)? out=None) -> Tensor");
@@ -1490,6 +1557,8 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("row_sort", row_sort);
     m.impl("row_topk", row_topk);
     m.impl("row_kth", row_kth);
+    m.impl("axis_reduce", axis_reduce);
+    m.impl("axis_scan", axis_scan);
     m.impl("run_length_encode", run_length_encode);
     m.impl("reduce_by_key", reduce_by_key);
     m.impl("scan_by_key", scan_by_key);

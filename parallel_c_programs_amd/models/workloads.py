@@ -9,6 +9,7 @@ from dataclasses import dataclass, field
 import torch
 
 from .. import ops
+from ..ops.vector import _axis_plan
 from ..parallel.collectives import global_scan
 from ..parallel.dist import Context
 
@@ -1390,10 +1391,85 @@ class RowSort(Workload):
         return {"elements_checked": self.x.numel(), "exact_vs_torch": ok, "check_passed": ok}
 
 
+class Axis(Workload):
+    """Reduce or scan along the middle extent of an [outer, n, inner] tensor per GPU (csrc/kernels/axis.hip): mode
+    "reduce" (ops.reduce(x, op, dim=1)) or "scan" (ops.scan(x, exclusive, dim=1, op=op)); op sum / min / max; dtype f32
+    (whole numbers in [-8, 8], or in [-1, 1] for n above 2^20, so a sum is exact in any order up to n = 2^24) or i32
+    (the full range: sums wrap). inner == 1 is the last-dimension case. route and chunk are the ops' (None picks by
+    shape). No communication (weak scaling)."""
+
+    MODES = ("reduce", "scan")
+
+    def __init__(self, ctx, outer=1 << 14, n=4096, inner=1, mode="reduce", op="sum", dtype="f32", exclusive=False,
+                 route=None, chunk=None, **_):
+        if mode not in self.MODES:
+            raise ValueError(f"axis mode {mode!r}: one of {self.MODES}")
+        if op not in ops.OP_CODES:
+            raise ValueError(f"axis op {op!r}: one of {sorted(ops.OP_CODES)}")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"axis dtype {dtype!r}: f32 or i32")
+        outer, n, inner = int(outer), int(n), int(inner)
+        if min(outer, n, inner) < 1:
+            raise ValueError(f"axis shape [{outer}, {n}, {inner}]: every extent at least 1")
+        super().__init__(ctx, {"outer": outer, "n": n, "inner": inner, "mode": mode, "op": op, "dtype": dtype,
+                               "exclusive": bool(exclusive), "route": route, "chunk": chunk}, "axis", "GB/s")
+        self.mode, self.op, self.exclusive, self.route, self.chunk = mode, op, bool(exclusive), route, chunk
+        g = torch.Generator(device=ctx.device).manual_seed(17000 + ctx.rank)
+        amp = 8 if n <= 1 << 20 else 1
+        self.x = torch.randint(-amp if dtype == "f32" else -(1 << 31), amp + 1 if dtype == "f32" else 1 << 31,
+                               (outer, n, inner), device=ctx.device, generator=g, dtype=torch.int64)
+        self.x = self.x.float() if dtype == "f32" else self.x.to(torch.int32)
+        self.exact = dtype == "i32" or op != "sum" or amp * n < 1 << 24
+        self.out = None
+        _axis_plan(mode, route, chunk, outer, n, inner, "axis")  # a route that cannot take the shape raises here
+
+    def step(self):
+        if self.mode == "reduce":
+            self.out = ops.reduce(self.x, self.op, dim=1, route=self.route, chunk=self.chunk)
+        else:
+            self.out = ops.scan(self.x, self.exclusive, dim=1, op=self.op, route=self.route, chunk=self.chunk)
+
+    def torch_step(self):
+        """The torch call this replaces (the vendor bar)."""
+        if self.mode == "reduce":
+            return {"sum": torch.sum, "min": torch.amin, "max": torch.amax}[self.op](self.x, 1)
+        if self.op == "sum":
+            return torch.cumsum(self.x, 1, dtype=self.x.dtype)
+        return (torch.cummin if self.op == "min" else torch.cummax)(self.x, 1).values
+
+    def work_per_step(self):
+        # the bytes a caller sees move: the input read once, and what is written
+        out = self.x.numel() if self.mode == "scan" else self.x.shape[0] * self.x.shape[2]
+        return float(4 * (self.x.numel() + out))
+
+    def check(self, reduce: bool = True):
+        """Every output of the timed step against the host path of the same op on a host copy: exactly, except a
+        float32 sum of more than 2^24 terms' worth of magnitude, which is held to the bound of any summation order,
+        terms * 2^-24 * sum |x|. Local only."""
+        xh, out = self.x.cpu(), self.out.cpu()
+        ref = ops.reduce(xh, self.op, dim=1) if self.mode == "reduce" else ops.scan(xh, self.exclusive, dim=1, op=self.op)
+        ok = out.dtype == ref.dtype and out.shape == ref.shape
+        if ok and self.exact:
+            ok = torch.equal(out, ref)
+        elif ok:
+            mag = xh.abs().double()
+            mag = mag.sum(1) if self.mode == "reduce" else torch.cumsum(mag, 1)
+            ok = bool(((out.double() - ref.double()).abs() <= xh.shape[1] * 2.0 ** -24 * mag).all())
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"elements_checked": self.out.numel(), "exact_vs_host": bool(self.exact), "check_passed": ok}
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gelems_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        return rep
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
              "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
-             "merge": Merge, "rowsort": RowSort}
+             "merge": Merge, "rowsort": RowSort, "axis": Axis}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

@@ -77,8 +77,15 @@ def dot(a: torch.Tensor, b: torch.Tensor, n_threads: int = 0) -> torch.Tensor:
     return torch.tensor(cpu_lib().pcmx_dot_omp(a.data_ptr(), b.data_ptr(), a.numel(), n_threads), dtype=torch.float32)
 
 
-def reduce(x: torch.Tensor, op: str = "sum") -> torch.Tensor:
-    """Global reduction of a float32/int32 tensor to a 0-d tensor (op in sum/min/max)."""
+def reduce(x: torch.Tensor, op: str = "sum", dim: int | None = None, keepdim: bool = False, route: str | None = None,
+           chunk: int | None = None) -> torch.Tensor:
+    """Global reduction of a float32/int32 tensor to a 0-d tensor (op in sum/min/max). dim=int: the reduction of every
+    row along dim, torch's shape (dim removed, or kept with size 1 under keepdim); keepdim, route and chunk go with dim
+    (the along-a-dimension section below)."""
+    if dim is not None:
+        return _axis_reduce(x, op, dim, keepdim, route, chunk)
+    if keepdim or route is not None or chunk is not None:
+        raise ValueError("reduce: keepdim, route and chunk are for the reduction along a dimension: they need dim=")
     code = OP_CODES[op]
     if x.is_cuda:
         return ops().reduce(x, code)
@@ -91,13 +98,20 @@ def reduce(x: torch.Tensor, op: str = "sum") -> torch.Tensor:
 
 
 def scan(x: torch.Tensor, exclusive: bool = False, init: torch.Tensor | None = None,
-         check: bool = False) -> torch.Tensor:
+         check: bool = False, dim: int | None = None, op: str = "sum", out: torch.Tensor | None = None,
+         route: str | None = None, chunk: int | None = None) -> torch.Tensor:
     """Prefix sum over the flattened tensor (decoupled look-back single pass on the GPU).
 
     ``init`` (a 1-element float32 tensor on the same device) is added to every output; the multi-GPU
     scan feeds its rank offset through it without a host round trip. ``check=True`` waits for the current
     stream and raises if this (or an earlier unchecked) scan on it gave up a look-back (scan_check).
+    ``dim=int``: the running op (sum, min, max; float32 or int32) of every row along dim, x's shape; op, out, route
+    and chunk go with dim (the along-a-dimension section below).
     """
+    if dim is not None:
+        return _axis_scan(x, op, exclusive, init, check, dim, out, route, chunk)
+    if op != "sum" or out is not None or route is not None or chunk is not None:
+        raise ValueError("scan: op, out, route and chunk are for the scan along a dimension: they need dim=")
     if x.is_cuda:
         y = ops().scan(x, exclusive, init)
         if check:
@@ -926,6 +940,182 @@ def run_positions(keys: torch.Tensor) -> torch.Tensor:
     head = _key_heads(keys)
     start = torch.cummax(torch.where(head, torch.arange(n), 0), 0).values if n else torch.arange(0)
     return (torch.arange(n) - start).int().reshape(keys.shape)
+
+
+# ---------------------------------------------------------------- reduce / scan along a dimension (dim=)
+# reduce(x, op, dim) and scan(x, dim=dim, op=op) work on every row along dim on its own: torch.sum / amin / amax (dim)
+# and torch.cumsum / cummin / cummax (dim).values, float32 or int32, with torch's shapes. The contiguous tensor is
+# viewed as [outer, n, inner] with the work along n and read where it lies for every dim (csrc/kernels/axis.hip; no
+# counterpart in the reference programs); a non-contiguous input is gathered first. No look-back, no block waits for
+# another, nothing can time out, so scan_check() has nothing of these calls to report. Nothing synchronises.
+#  * int32 sums wrap mod 2^32 and int32 results are exact; float32 min / max are exact where a row holds no NaN; a row
+#    (for scan: a prefix) that holds a NaN gives a NaN (which NaN is unspecified, as is the sign of a zero min / max);
+#    a float32 sum uses a fixed association order (axis.hip's header) that depends on size(dim), the inner extent and
+#    the route only: the same row gives the same bits wherever it stands. Rows never mix. Fewer than 2^31 elements.
+#  * A 1-D tensor with dim=0 is one long row: the int32 and min / max scans of a flat tensor. reduce(x) and scan(x)
+#    without dim stay the flat kernels (the look-back scan, the two-pass reduce).
+#  * route (tests and the lab) forces a GPU route and raises ValueError when it cannot take the shape; it is validated
+#    on CPU tensors too, which otherwise ignore it. inner == 1: "group" (G lanes per row, n <= AXIS_GROUP_MAX_N),
+#    "block" (one block per row, n <= AXIS_BLOCK_MAX_N), "split" (chunks of `chunk` elements of a row over blocks, a
+#    multiple of 1024, then a fold / carry pass). inner > 1: "column" (a thread walks down 4 adjacent columns),
+#    "column_split" (chunks of `chunk` >= AXIS_COLUMN_MIN_CHUNK rows over threads, then a fold / carry pass).
+#  * route=None picks by the constants below (_axis_route), each set from the lab's A/B of the two routes it separates
+#    on one MI355X (scripts/axis_lab.py, profiles/r17_axis/README.md; float32 sums, median ms of 5 interleaved runs,
+#    reduce / scan):
+#    - AXIS_GROUP_N, AXIS_GROUP_SCAN_N: 2^24 elements, group against block: 0.017 / 0.152 and 0.029 / 0.146 at n = 128;
+#      0.017 / 0.040 and 0.028 / 0.038 at 512; 0.016 / 0.024 and 0.030 / 0.028 at 1024; 0.017 / 0.020 and 0.032 / 0.029 at
+#      2048; 0.020 / 0.018 and 0.031 / 0.031 at 4096 (a second run: scans 0.031 / 0.044, 0.036 / 0.032, 0.034 / 0.031,
+#      0.036 / 0.031). The reduce keeps group to 2048, the scan to 512: block scans are 7%-12% faster from 1024.
+#    - AXIS_SPLIT_MIN_N, AXIS_SPLIT_ROWS: block against split at 1 / 8 / 64 / 256 / 1024 rows: n = 32768 block at every
+#      row count (0.010 / 0.013 to 0.027 / 0.031 reduce, 0.025 / 0.030 to 0.056 / 0.083 scan); n = 131072 split up to 256
+#      rows (reduce 0.023 / 0.012, 0.037 / 0.021, 0.052 / 0.023, 0.053 / 0.031; scan 0.088 / 0.032 to 0.140 / 0.085) and
+#      block at 1024 rows (0.085 / 0.105 and 0.205 / 0.310). 512 lies between the two measured row counts and is itself
+#      NOT MEASURED; 65536-element rows are not measured either.
+#    - AXIS_BLOCK_MAX_N: at 2^20 elements per row split wins at every measured row count (64 rows 0.378 / 0.058 and
+#      0.945 / 0.160); [1024, 2^20] is not measured: the border above 256 rows is a guess.
+#    - AXIS_SPLIT_CHUNK: 8192 / 32768 / 131072 at [8, 2^24] 0.108 / 0.105 / 0.088 and 0.293 / 0.308 / 0.287, at [1, 2^26]
+#      0.060 / 0.056 / 0.063 and 0.160 / 0.163 / 0.216, at [64, 2^20] 0.057 / 0.058 / 0.068 and 0.155 / 0.161 / 0.222: no
+#      chunk wins everywhere, 32768 is never more than 7% (reduce: 19%) behind the best.
+#    - AXIS_COLUMN_MIN_BLOCKS (reduce), column against column_split along dim 0: [1024, 16384] (64 blocks) 0.094 / 0.026,
+#      [1024, 65536] and [64, 1024, 1024] along dim 1 (256 blocks) 0.105 / 0.052 and 0.110 / 0.051, [256, 262144] (1024
+#      blocks) 0.044 / 0.044. Level at 1024, twice as slow at 256; 512 is NOT MEASURED.
+#    - AXIS_COLUMN_MIN_UNITS (scan): [1024, 65536] (16384 threads) 0.541 / 0.237, [256, 262144] (65536) 0.179 / 0.176.
+#    - AXIS_COLUMN_SPLIT_MIN_N is a guess and NOT MEASURED ([32, 262144]: 0.011 / 0.012 and 0.029 / 0.030, level).
+#  * Measured against torch on one MI355X (profiles/r17_axis/README.md; float32, torch.sum / amax / cumsum /
+#    cummax(dim)): along the last dim [2^20, 32] 5.3x / 5.5x / 53x / 59x, [2^16, 512] 1.2x-2.6x, [1024, 32768] 1.3x and
+#    6.7x, [8, 2^24] 37x-164x, at 0.79x-1.31x the time of ops.copy_ of the same bytes for rows that fit a group or a
+#    block; along dim 0 [4096, 4096] 1.0x / 1.2x / 16x / 17x, [2^20, 64] 1.3x / 1.3x / 1060x, [64, 2^20] 1.0x-1.9x, [64,
+#    1024, 1024] along dim 1 1.1x-3.1x; 1.5x-18x faster than movedim().contiguous() and the row route in every cell.
+#    SLOWER than torch: sum / amax of [16384, 4096] (0.053 against 0.051 ms, 0.96x-0.97x). A scan on a split route reads
+#    the input twice: 1.8x the copy floor. SLOWER than the flat ops on one row of 2^28: reduce 0.206 against ops.reduce
+#    0.157 ms, scan 0.625 against ops.scan 0.355 ms (torch 0.274 / 0.708): flat float32 sums keep reduce(x) / scan(x);
+#    dim=0 of a flat tensor is for int32 and min / max.
+AXIS_GROUP_MAX_N = 4096          # PCMX_AXIS_GROUP_MAX_N: the group kernel's limit when forced
+AXIS_GROUP_N = 2048              # PCMX_AXIS_GROUP_N: reduce: rows up to here take group, longer ones block
+AXIS_GROUP_SCAN_N = 512          # PCMX_AXIS_GROUP_SCAN_N: scan: the same border
+AXIS_BLOCK_MAX_N = 1 << 20       # PCMX_AXIS_BLOCK_MAX_N: longer rows always take split
+AXIS_SPLIT_ROWS = 512            # PCMX_AXIS_SPLIT_ROWS: with fewer rows than this ...
+AXIS_SPLIT_MIN_N = 1 << 17       # PCMX_AXIS_SPLIT_MIN_N: ... rows from this length take split
+AXIS_SPLIT_CHUNK = 32768         # PCMX_AXIS_SPLIT_CHUNK: the default chunk of split
+AXIS_COLUMN_MIN_UNITS = 65536    # PCMX_AXIS_COLUMN_MIN_UNITS: scan: column from this many threads (outer * ceil(inner / 4))
+AXIS_COLUMN_MIN_BLOCKS = 1024    # PCMX_AXIS_COLUMN_MIN_BLOCKS: reduce: column from this many blocks (outer * 64-quad tiles)
+AXIS_COLUMN_SPLIT_MIN_N = 64     # PCMX_AXIS_COLUMN_SPLIT_MIN_N (guess, NOT MEASURED): ... or when n is below this
+AXIS_COLUMN_MIN_CHUNK = 16       # PCMX_AXIS_COLUMN_MIN_CHUNK: the smallest chunk of column_split
+AXIS_GROUP, AXIS_BLOCK, AXIS_SPLIT, AXIS_COLUMN, AXIS_COLUMN_SPLIT = 1, 2, 3, 4, 5  # PCMX_AXIS_*
+_AXIS_ROUTE_CODE = {"group": AXIS_GROUP, "block": AXIS_BLOCK, "split": AXIS_SPLIT, "column": AXIS_COLUMN,
+                    "column_split": AXIS_COLUMN_SPLIT}
+_AXIS_TILE = 1024                # split chunks are whole tiles of the block kernel
+
+
+def _axis_route(kind: str, outer: int, n: int, inner: int) -> str:
+    """The default route of reduce / scan along a dimension for the [outer, n, inner] view (kind: "reduce" or "scan":
+    the column reduce is a block-cooperative kernel, the column scan a thread per 4 columns, so their borders differ)."""
+    if kind not in ("reduce", "scan"):
+        raise ValueError(f"kind must be 'reduce' or 'scan', got {kind!r}")
+    if inner == 1:
+        if n <= (AXIS_GROUP_SCAN_N if kind == "scan" else AXIS_GROUP_N):
+            return "group"
+        if n > AXIS_BLOCK_MAX_N or (outer < AXIS_SPLIT_ROWS and n >= AXIS_SPLIT_MIN_N):
+            return "split"
+        return "block"
+    quads = (inner + 3) // 4
+    if kind == "reduce":  # a block is min(64, quads rounded up to a power of two) quads wide (axis.hip: col_lanes)
+        fills = outer * -(-quads // min(64, 1 << (quads - 1).bit_length())) >= AXIS_COLUMN_MIN_BLOCKS
+    else:
+        fills = outer * quads >= AXIS_COLUMN_MIN_UNITS
+    return "column" if fills or n < AXIS_COLUMN_SPLIT_MIN_N else "column_split"
+
+
+def _axis_plan(kind: str, route, chunk, outer: int, n: int, inner: int, name: str):
+    """(route code, chunk) for the kernels after validating route and chunk against the shape; 0 = the default."""
+    if route is not None and route not in _AXIS_ROUTE_CODE:
+        raise ValueError(f"{name}: route must be None or one of {sorted(_AXIS_ROUTE_CODE)}, got {route!r}")
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int)):
+        raise TypeError(f"{name}: chunk must be an int or None, got {type(chunk).__name__}")
+    resolved = route if route is not None else _axis_route(kind, outer, n, inner)
+    if (resolved in ("group", "block", "split")) != (inner == 1):
+        raise ValueError(f"{name}: route {route!r} is for {'the last dimension (inner extent 1)' if inner != 1 else 'an inner extent above 1'}, "
+                         f"the view is [{outer}, {n}, {inner}]")
+    limit = {"group": AXIS_GROUP_MAX_N, "block": AXIS_BLOCK_MAX_N}.get(resolved)
+    if limit is not None and n > limit:
+        raise ValueError(f"{name}: route {route!r} takes rows of at most {limit} elements, got {n}")
+    if chunk is not None:
+        if resolved == "split":
+            if chunk < _AXIS_TILE or chunk % _AXIS_TILE:
+                raise ValueError(f"{name}: the chunk of route 'split' is a positive multiple of {_AXIS_TILE}, got {chunk}")
+        elif resolved == "column_split":
+            if chunk < AXIS_COLUMN_MIN_CHUNK:
+                raise ValueError(f"{name}: the chunk of route 'column_split' is at least {AXIS_COLUMN_MIN_CHUNK}, got {chunk}")
+        else:
+            raise ValueError(f"{name}: chunk is for the split routes, the route here is {resolved!r}")
+    return (0 if route is None else _AXIS_ROUTE_CODE[route]), (0 if chunk is None else chunk)
+
+
+def _axis_view(x: torch.Tensor, dim, op, name: str):
+    """(outer, n, inner, dim normalised) of the [outer, n, inner] view along dim, after the checks of x, op and dim."""
+    if isinstance(dim, bool) or not isinstance(dim, int):
+        raise TypeError(f"{name}: dim must be an int or None, got {type(dim).__name__}")
+    if x.dim() < 1 or not -x.dim() <= dim < x.dim():
+        raise IndexError(f"{name}: dim {dim} is out of range for a tensor with {x.dim()} dimensions")
+    if x.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name}: x must be float32 or int32, got {x.dtype}")
+    if op not in OP_CODES:
+        raise ValueError(f"{name}: op must be one of {sorted(OP_CODES)}, got {op!r}")
+    if x.numel() >= 1 << 31:
+        raise ValueError(f"{name}: x has {x.numel()} elements; offsets are 31-bit (fewer than 2^31)")
+    d = dim % x.dim()
+    return int(torch.Size(x.shape[:d]).numel()), x.shape[d], int(torch.Size(x.shape[d + 1:]).numel()), d
+
+
+def _wrap_i32(t: torch.Tensor) -> torch.Tensor:
+    return (((t + (1 << 31)) % (1 << 32)) - (1 << 31)).int()
+
+
+def _axis_reduce(x: torch.Tensor, op, dim, keepdim, route, chunk) -> torch.Tensor:
+    outer, n, inner, d = _axis_view(x, dim, op, "reduce")
+    code, chunk = _axis_plan("reduce", route, chunk, outer, n, inner, "reduce")
+    if n == 0 and op != "sum":
+        raise ValueError(f"reduce: {op} along a dimension of size 0 has no identity")
+    x3 = x.contiguous().view(outer, n, inner)
+    if x.is_cuda:
+        res = ops().axis_reduce(x3, OP_CODES[op], code, chunk)
+    elif op == "sum":
+        res = _wrap_i32(x3.long().sum(1)) if x.dtype == torch.int32 else x3.double().sum(1).float()
+    else:
+        res = torch.amin(x3, 1) if op == "min" else torch.amax(x3, 1)
+    shape = list(x.shape)
+    shape[d:d + 1] = [1] if keepdim else []
+    return res.reshape(shape)
+
+
+def _axis_scan(x: torch.Tensor, op, exclusive, init, check, dim, out, route, chunk) -> torch.Tensor:
+    if init is not None:
+        raise ValueError("scan: init is the single offset of the flat multi-GPU scan; with dim it must be None")
+    outer, n, inner, d = _axis_view(x, dim, op, "scan")
+    code, chunk = _axis_plan("scan", route, chunk, outer, n, inner, "scan")
+    _check_scan_out(out, x)
+    exclusive = bool(exclusive)
+    x3 = x.contiguous().view(outer, n, inner)
+    if x.is_cuda:
+        res = ops().axis_scan(x3, OP_CODES[op], exclusive, code, chunk, out)
+        if check:
+            scan_check(x.device)
+        return out if out is not None else res.view(x.shape)
+    if x3.numel() == 0:
+        res = x3.clone()
+    else:
+        if op == "sum":
+            incl = torch.cumsum(x3.long() if x.dtype == torch.int32 else x3.double(), 1)
+        else:
+            incl = (torch.cummin if op == "min" else torch.cummax)(x3, 1).values
+        if exclusive:
+            ident = 0 if op == "sum" else _SCAN_IDENTITY[op][0 if x.dtype == torch.float32 else 1]
+            incl = torch.cat([torch.full_like(incl[:, :1], ident), incl[:, :-1]], 1)
+        res = incl if op != "sum" else (_wrap_i32(incl) if x.dtype == torch.int32 else incl.float())
+    if out is None:
+        return res.view(x.shape)
+    out.view(-1).copy_(res.reshape(-1))
+    return out
 
 
 # ---------------------------------------------------------------- histograms (bincount / histc / explicit edges)
