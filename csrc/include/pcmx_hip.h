@@ -345,6 +345,34 @@ long long pcmx_searchsorted_workspace_bytes(long long n, long long m, int needle
 int pcmx_searchsorted_b32(const void* sorted_keys, long long n, const void* needles, long long m, int32_t* out,
                           int key_type, int right, int descending, int needles_sorted, void* workspace, hipStream_t s);
 
+/* ---------------------------------------------------------------- reduction over ragged segments (offsets) */
+/* out[j] = op over x[offsets[j], offsets[j+1]) for j < S: the segments of a CSR row_ptr, torch.segment_reduce with
+ * offsets= (csrc/kernels/ragged.hip). offsets holds S + 1 int32 values in device memory with the PRECONDITION
+ * 0 <= offsets[0] <= ... <= offsets[S] <= n; elements before offsets[0] and from offsets[S] on are not read. op is
+ * PCMX_OP_SUM / MIN / MAX. An empty segment gives the identity: +0.0 / 0 for SUM, +inf / INT32_MAX for MIN, -inf /
+ * INT32_MIN for MAX. int32 sums wrap mod 2^32 and int32 results are exact; float32 min / max are exact and hand on a
+ * NaN inside its segment only; a float32 sum uses a fixed association order that may depend on where the segment lies
+ * relative to the tiles and never on timing: the same input gives the same bits on every call, and a NaN or inf in one
+ * segment never reaches another. The list of segment ends is merged with the element indices and every block takes
+ * the same number of steps of that path, whatever the segment lengths are. Four launches on the stream (tile borders,
+ * tiles, a one-block scan of the tile summaries, the carry into the first segment every tile closed); no block waits
+ * for another, there are no float atomics and no err_flag. The precondition is not checked: offsets that break it
+ * give an unspecified result, but every load and store stays inside x[0, n), offsets[0, S], out[0, S) and the
+ * workspace. x and offsets 4-B aligned, out and the workspace (pcmx_segment_workspace_bytes, one call in flight per
+ * workspace) 16-B aligned, out must not overlap an input, n >= 0, S >= 0, n + S < 2^31, a valid op, no NULL pointer
+ * (x may be NULL when n == 0) (else PCMX_ERR_ARG, nothing launched); S == 0 returns 0 and touches nothing; n == 0
+ * with S > 0 writes S identities. */
+long long pcmx_segment_workspace_bytes(long long n, long long S);
+int pcmx_segment_reduce_f32(const float* x, long long n, const int32_t* offsets, long long S, int op, float* out,
+                            void* workspace, hipStream_t s);
+int pcmx_segment_reduce_i32(const int32_t* x, long long n, const int32_t* offsets, long long S, int op, int32_t* out,
+                            void* workspace, hipStream_t s);
+/* The head flags of the same offsets for pcmx_scan_by_key_* with PCMX_HEADS_FROM_FLAGS: heads[0, n) is zeroed, then
+ * heads[offsets[j]] = 1 for every j <= S with 0 <= offsets[j] < n (the store is bounded by n itself, so offsets that
+ * break the precondition touch nothing outside heads). offsets 4-B aligned, n and S < 2^31, no NULL pointer (else
+ * PCMX_ERR_ARG, nothing launched); n == 0 returns 0 and touches nothing. */
+int pcmx_segment_heads(const int32_t* offsets, long long S, long long n, unsigned char* heads, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

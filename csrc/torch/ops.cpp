@@ -938,6 +938,70 @@ at::Tensor searchsorted(const at::Tensor& sorted, const at::Tensor& values, bool
     return has_out ? merge_finish(out, dest) : dest.view(values.sizes());
 }
 
+// ---------------------------------------------------------------- reduction over ragged segments (offsets)
+// out[j] = op over x.flatten()[offsets[j] : offsets[j+1]] (csrc/kernels/ragged.hip). x and offsets are read where they
+// lie (element alignment is enough). `out` (1-D, contiguous, at least S elements, x's dtype) is returned as out[:S]
+// and never written past S; one that is not 16-B aligned is written through a temporary. The offsets are not looked
+// at on the host: nothing synchronises, and there is no error word.
+at::Tensor segment_offsets(const at::Tensor& offsets, const at::Tensor& x, const char* what) {
+    check_gpu(offsets, "offsets", at::kInt);
+    TORCH_CHECK(offsets.device() == x.device(), what, ": offsets must be on ", x.device());
+    TORCH_CHECK(offsets.dim() == 1 && offsets.is_contiguous() && offsets.numel() >= 1, what,
+                ": offsets must be 1-D and contiguous with at least one entry");
+    return offsets;
+}
+
+at::Tensor segment_reduce(const at::Tensor& x, const at::Tensor& offsets, int64_t op, const c10::optional<at::Tensor>& out) {
+    TORCH_CHECK(x.is_cuda(), "segment_reduce: x must be a GPU tensor");
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kInt, "segment_reduce: x has dtype ", x.scalar_type(),
+                ", expected float32 or int32");
+    TORCH_CHECK(op >= PCMX_OP_SUM && op <= PCMX_OP_MAX, "segment_reduce: op code ", op);
+    TORCH_CHECK(x.is_contiguous(), "segment_reduce: x must be contiguous");
+    const at::DeviceGuard g(x.device());
+    at::Tensor oc = segment_offsets(offsets, x, "segment_reduce");
+    const int64_t n = x.numel(), S = oc.numel() - 1;
+    TORCH_CHECK(n + S < (1LL << 31), "segment_reduce: elements and segments together must be fewer than 2^31");
+    const bool has_out = out.has_value() && out->defined();
+    if (has_out) {
+        check_gpu(*out, "out", x.scalar_type());
+        TORCH_CHECK(out->device() == x.device() && out->dim() == 1 && out->is_contiguous() && out->numel() >= S,
+                    "segment_reduce: out must be 1-D, contiguous, on x's device, with at least ", S, " elements");
+        TORCH_CHECK(!(S && overlaps(*out, x)) && !overlaps(*out, oc), "segment_reduce: out must not overlap an input");
+    }
+    at::Tensor xc = x.view(-1);
+    at::Tensor dest = has_out && !(reinterpret_cast<uintptr_t>(out->data_ptr()) & 15u) ? out->narrow(0, 0, S)
+                                                                                      : at::empty({S}, x.options());
+    if (S != 0) {
+        auto ws = workspace(x, pcmx_segment_workspace_bytes(n, S));
+        hipStream_t stream = cur_stream(x);
+        if (x.scalar_type() == at::kFloat)
+            check_rc(pcmx_segment_reduce_f32(n ? xc.data_ptr<float>() : nullptr, n, oc.data_ptr<int32_t>(), S, (int)op,
+                                             dest.data_ptr<float>(), ws.data_ptr(), stream),
+                     "segment_reduce");
+        else
+            check_rc(pcmx_segment_reduce_i32(n ? xc.data_ptr<int32_t>() : nullptr, n, oc.data_ptr<int32_t>(), S, (int)op,
+                                             dest.data_ptr<int32_t>(), ws.data_ptr(), stream),
+                     "segment_reduce");
+    }
+    if (!has_out) return dest;
+    at::Tensor head = out->narrow(0, 0, S);
+    if (S != 0 && dest.data_ptr() != out->data_ptr()) head.copy_(dest);
+    return head;
+}
+
+// uint8 [n]: 1 at every offsets[j] < n, 0 elsewhere: the head flags segmented_scan takes
+at::Tensor segment_heads(const at::Tensor& offsets, int64_t n, const at::Tensor& like) {
+    TORCH_CHECK(like.is_cuda(), "segment_heads: the values must be a GPU tensor");
+    const at::DeviceGuard g(like.device());
+    at::Tensor oc = segment_offsets(offsets, like, "segment_heads");
+    TORCH_CHECK(n >= 0 && n < (1LL << 31) && oc.numel() < (1LL << 31), "segment_heads: fewer than 2^31 elements and offsets");
+    at::Tensor heads = at::empty({n}, like.options().dtype(at::kByte));
+    if (n != 0)
+        check_rc(pcmx_segment_heads(oc.data_ptr<int32_t>(), oc.numel() - 1, n, heads.data_ptr<uint8_t>(), cur_stream(like)),
+                 "segment_heads");
+    return heads;
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -1508,6 +1572,8 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("merge_index(Tensor a, Tensor b, bool descending=False, bool want_keys=True, Tensor(a!)? out_keys=None, Tensor(b!)? out_idx=None) -> (Tensor, Tensor)");
     m.def("merge_pairs(Tensor keys_a, Tensor values_a, Tensor keys_b, Tensor values_b, bool descending=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_values=None) -> (Tensor, Tensor)");
     m.def("searchsorted(Tensor sorted_sequence, Tensor values, bool right=False, bool descending=False, bool values_sorted=False, Tensor(a!)? out=None) -> Tensor");
+    m.def("segment_reduce(Tensor x, Tensor offsets, int op, Tensor(a!)? out=None) -> Tensor");
+    m.def("segment_heads(Tensor offsets, int n, Tensor like) -> Tensor");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -1571,6 +1637,8 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("merge_index", merge_index);
     m.impl("merge_pairs", merge_pairs);
     m.impl("searchsorted", searchsorted);
+    m.impl("segment_reduce", segment_reduce);
+    m.impl("segment_heads", segment_heads);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

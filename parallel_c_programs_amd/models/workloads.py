@@ -9,6 +9,7 @@ from dataclasses import dataclass, field
 import torch
 
 from .. import ops
+from ..ops.sparse import powerlaw_row_ptr
 from ..ops.vector import _axis_plan
 from ..parallel.collectives import global_scan
 from ..parallel.dist import Context
@@ -1466,10 +1467,94 @@ class Axis(Workload):
         return rep
 
 
+class Ragged(Workload):
+    """Reduction over ragged segments given by offsets (csrc/kernels/ragged.hip): ops.segment_reduce(x, offsets, op) on
+    n elements per GPU. dist places the segment borders: "uniform" (n / mean_len borders drawn uniformly: lengths vary,
+    some segments are empty), "equal" (every segment mean_len long, the last one with the remainder), "powerlaw" (the row lengths of
+    ops.sparse.powerlaw_row_ptr, the SpMV matrices' rows) or "empty" (S = 4 n: most segments are empty). op sum / min /
+    max; dtype f32 (whole numbers in [-8, 8], or in [-1, 1] when the longest segment could otherwise leave the exact
+    range) or i32 (the full range: sums wrap). No communication (weak scaling)."""
+
+    DISTS = ("uniform", "equal", "powerlaw", "empty")
+
+    def __init__(self, ctx, n=1 << 28, mean_len=100.0, dist="uniform", op="sum", dtype="f32", **_):
+        if dist not in self.DISTS:
+            raise ValueError(f"ragged dist {dist!r}: one of {self.DISTS}")
+        if op not in ops.OP_CODES:
+            raise ValueError(f"ragged op {op!r}: one of {sorted(ops.OP_CODES)}")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"ragged dtype {dtype!r}: f32 or i32")
+        n, mean_len = int(n), float(mean_len)
+        if n < 1 or mean_len < 1.0:
+            raise ValueError(f"ragged n = {n}, mean_len = {mean_len}: both at least 1")
+        super().__init__(ctx, {"n": n, "mean_len": mean_len, "dist": dist, "op": op, "dtype": dtype}, "ragged", "GB/s")
+        self.op = op
+        dev = ctx.device
+        g = torch.Generator(device=dev).manual_seed(18000 + ctx.rank)
+        s = 4 * n if dist == "empty" else max(1, int(n / mean_len))
+        if dist == "equal":
+            off = torch.clamp(torch.arange(s + 1, device=dev, dtype=torch.int64) * int(mean_len), max=n)
+            off[-1] = n  # the last segment takes the remainder
+        elif dist == "powerlaw":
+            off = torch.clamp(powerlaw_row_ptr(s, n, seed=18 + ctx.rank), max=n).to(dev)
+        else:
+            cuts = torch.sort(torch.randint(0, n + 1, (s - 1,), device=dev, generator=g, dtype=torch.int32)).values
+            off = torch.cat([cuts.new_zeros(1), cuts, cuts.new_full((1,), n)])
+        self.offsets = off.to(torch.int32).contiguous()
+        self.offsets64 = None  # torch_step's copy, made on first use
+        longest = int((self.offsets[1:] - self.offsets[:-1]).max())
+        amp = 8 if 8 * longest < 1 << 24 else 1
+        self.exact = dtype == "i32" or op != "sum" or amp * longest < 1 << 24
+        self.x = torch.randint(-amp if dtype == "f32" else -(1 << 31), amp + 1 if dtype == "f32" else 1 << 31, (n,),
+                               device=dev, generator=g, dtype=torch.int64)
+        self.x = self.x.float() if dtype == "f32" else self.x.to(torch.int32)
+        self.out = None
+
+    def segments(self) -> int:
+        return self.offsets.numel() - 1
+
+    def step(self):
+        self.out = ops.segment_reduce(self.x, self.offsets, self.op)
+
+    def torch_step(self):
+        """The torch call this replaces (the vendor bar); torch.segment_reduce takes floating types only."""
+        if self.offsets64 is None:
+            self.offsets64 = self.offsets.long()
+        return torch.segment_reduce(self.x, self.op, offsets=self.offsets64)
+
+    def work_per_step(self):
+        # the bytes a caller sees move: the elements and the offsets read once, one result per segment written
+        return float(4 * (self.x.numel() + 2 * self.segments() + 1))
+
+    def check(self, reduce: bool = True):
+        """Every result of the timed step against the host path on a host copy: exactly, except a float32 sum whose
+        longest segment could leave the exact range, which is held to twice the bound of any summation order, terms *
+        2^-24 * sum |x| per segment (the host path sums in float32 too). Local only."""
+        xh, oh, out = self.x.cpu(), self.offsets.cpu(), self.out.cpu()
+        ref = ops.segment_reduce(xh, oh, self.op)
+        ok = out.dtype == ref.dtype and out.shape == ref.shape
+        if ok and self.exact:
+            ok = torch.equal(out, ref)
+        elif ok:
+            mag = ops.segment_reduce(xh.abs(), oh, "sum").double()
+            terms = (oh[1:] - oh[:-1]).double()
+            ok = bool(((out.double() - ref.double()).abs() <= 2.0 * terms * 2.0 ** -24 * mag).all())  # both are float32 sums
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"elements_checked": self.out.numel(), "exact_vs_host": bool(self.exact), "check_passed": ok}
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gelems_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        rep["segments"] = self.segments()
+        return rep
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
              "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
-             "merge": Merge, "rowsort": RowSort, "axis": Axis}
+             "merge": Merge, "rowsort": RowSort, "axis": Axis, "ragged": Ragged}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

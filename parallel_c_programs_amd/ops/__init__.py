@@ -7,10 +7,11 @@ from .sparse import CSR, SlicedCSR, banded_csr, create_vector, powerlaw_csr, spm
 from .stencil import init_grid, stencil5_reference, stencil5_step_, stencil5x2_step_, stencil5_fused_step_, stencil5_fused_spans_
 # sort_keys / sort / argsort / sort_by_key / topk / kth_value take dim=int for the row-wise forms (one wave or one block
 # per row, csrc/kernels/rowsort.hip); their route constants (ROWSORT_*, ROW_TOPK_*) live in .vector. reduce / scan take
-# dim=int for the forms along a dimension (csrc/kernels/axis.hip); their route constants (AXIS_*) live there too
+# dim=int for the forms along a dimension (csrc/kernels/axis.hip); their route constants (AXIS_*) live there too.
+# segment_reduce / segment_scan take ragged segments by offsets (csrc/kernels/ragged.hip; RAGGED_TILE, RAGGED_LANE_ITEMS)
 from .vector import (CMP_CODES, OP_CODES, argsort, axpy_, bincount, bucketize, compact, compact_indices, compact_where, copy_, dot, fill_,
                      gather_, histc, histogram, kth_value, merge, merge_by_key, merge_keys, rand_uniform_, reduce, reduce_by_key, run_length_encode, run_positions, scan,
-                     scan_by_key, scan_check, searchsorted, segmented_scan, select, select_indices, sort, sort_by_key, sort_keys, sum_by_key,
+                     scan_by_key, scan_check, searchsorted, segment_reduce, segment_scan, segmented_scan, select, select_indices, sort, sort_by_key, sort_keys, sum_by_key,
                      topk, unique, unique_consecutive, vadd, vmul)
 
 __all__ = [
@@ -27,4 +28,5 @@ __all__ = [
     "scan_by_key", "segmented_scan", "run_positions",
     "bincount", "histc", "histogram",
     "merge_keys", "merge", "merge_by_key", "searchsorted", "bucketize",
+    "segment_reduce", "segment_scan",
 ]

@@ -1458,3 +1458,144 @@ def searchsorted(sorted_sequence: torch.Tensor, values: torch.Tensor, right: boo
 def bucketize(values: torch.Tensor, boundaries: torch.Tensor, right: bool = False) -> torch.Tensor:
     """torch.bucketize with int32 results: searchsorted(boundaries, values, right) for ascending boundaries."""
     return searchsorted(boundaries, values, right=right)
+
+
+# ---------------------------------------------------------------- reduction / scan over ragged segments (offsets)
+# The third way of reducing in pieces, beside runs of equal keys (reduce_by_key, scan_by_key) and equal-length rows
+# (dim=): ragged segments given by an offsets tensor, the form of CSR.row_ptr, powerlaw_row_ptr and the starts of
+# run_length_encode, and of torch.segment_reduce(data, reduce, offsets=...). Segment j is
+# x.flatten()[offsets[j] : offsets[j+1]]; result j belongs to segment j, empty segments included. On the GPU the list
+# of segment ends is merged with the element indices and every block takes RAGGED_TILE steps of that path, so one
+# segment of 2^28, 2^28 segments of one, power-law rows and mostly empty segments all load the blocks evenly
+# (csrc/kernels/ragged.hip; no counterpart in the reference programs). No look-back, no block waits for another,
+# nothing synchronises.
+#  * PRECONDITION: 0 <= offsets[0] <= ... <= offsets[S] <= n. Elements before offsets[0] and from offsets[S] on belong
+#    to no segment and are not read. It is not checked unless validate=True (one host sync); offsets that break it
+#    give an unspecified result, but nothing outside the tensors is touched.
+#  * An empty segment gives the identity: +0.0 / 0 for sum, +inf / INT32_MAX for min, -inf / INT32_MIN for max (for
+#    floats the values of torch.segment_reduce).
+#  * int32 sums wrap mod 2^32; int32 results and float32 min / max are exact; float32 min / max hand on a NaN inside
+#    its segment only; a float32 sum uses a fixed association order that may depend on where the segment lies relative
+#    to the tiles, never on timing: the same input gives the same bits on every call. A NaN or inf in one segment never
+#    reaches another.
+#  * Measured on one MI355X at 2^28 float32 elements (profiles/r18_ragged/README.md; ours / torch.segment_reduce /
+#    reduce_by_key on expanded ids, ms): equal segments of 100 0.44 / 1.75 / 0.73, one segment 0.39 / 90.3 / 0.73,
+#    power-law rows of mean 100 0.43 / 1.79 / n/a, S = 4 n 3.01 (torch raises from 2^26 segments); 2.1x-2.6x the time
+#    of ops.copy_ of the same bytes in every case. SLOWER than torch at 2684 segments of 10^5 (0.378 against 0.196 ms)
+#    and than the reduce_by_key route at length 1 (1.132 against 1.062 ms, its id expansion not counted).
+RAGGED_TILE = 4352        # csrc/kernels/ragged.hip kTile: path steps (elements + segment ends) per block; not measured
+RAGGED_LANE_ITEMS = 17    # kItems: path steps per lane (256 lanes per block); not measured
+RAGGED_MAX_PATH = (1 << 31) - 1
+
+
+def _check_segments(x: torch.Tensor, offsets: torch.Tensor, op: str, name: str) -> int:
+    """The number of segments after the argument checks the two ops share."""
+    if x.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name}: x must be float32 or int32, got {x.dtype}")
+    if offsets.dtype != torch.int32:
+        raise TypeError(f"{name}: offsets must be int32, got {offsets.dtype}")
+    if op not in OP_CODES:
+        raise ValueError(f"op must be one of {sorted(OP_CODES)}, got {op!r}")
+    if offsets.device != x.device:
+        raise ValueError(f"{name}: offsets are on {offsets.device}, x on {x.device}")
+    if offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+        raise ValueError(f"{name}: offsets must be 1-D and contiguous with S + 1 >= 1 entries, got shape "
+                         f"{tuple(offsets.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name}: x must be contiguous")
+    s = offsets.numel() - 1
+    if x.numel() + s > RAGGED_MAX_PATH:
+        raise ValueError(f"{name}: {x.numel()} elements and {s} segments; path positions are int32 (fewer than 2^31 "
+                         "together)")
+    return s
+
+
+def _validate_offsets(offsets: torch.Tensor, n: int) -> None:
+    """Raises ValueError naming the first entry that breaks 0 <= offsets[0] <= ... <= offsets[S] <= n (one host sync)."""
+    o = offsets.long()
+    lower = torch.cat([o.new_zeros(1), o[:-1]])  # what entry k must not lie below
+    bad = (o < lower) | (o > n)
+    k = int(torch.argmax(bad.int())) if bool(bad.any()) else -1
+    if k < 0:
+        return
+    v = int(offsets[k])
+    if v > n:
+        raise ValueError(f"offsets[{k}] = {v} lies above the {n} elements of x")
+    if k == 0 or v < 0:
+        raise ValueError(f"offsets[{k}] = {v} is negative")
+    raise ValueError(f"offsets[{k}] = {v} lies below offsets[{k - 1}] = {int(offsets[k - 1])}")
+
+
+def _host_segment_reduce(x: torch.Tensor, offsets: torch.Tensor, op: str) -> torch.Tensor:
+    """The CPU path: int32 sums through int64 prefix differences (exact, wrapped); everything else through
+    torch.segment_reduce, int32 min / max on a float64 copy (exact) with the int32 identities for empty segments."""
+    xf, s = x.reshape(-1), offsets.numel() - 1
+    ident = _SCAN_IDENTITY[op][0 if x.dtype == torch.float32 else 1]
+    if s == 0 or xf.numel() == 0:
+        return torch.full((s,), ident, dtype=x.dtype)
+    o = offsets.long()
+    if x.dtype == torch.float32:
+        return torch.segment_reduce(xf, op, offsets=o)
+    if op == "sum":
+        c = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(xf.long(), 0)])
+        return _wrap_i32(c[o[1:]] - c[o[:-1]])
+    r = torch.segment_reduce(xf.double(), op, offsets=o)
+    return torch.where(o[1:] == o[:-1], torch.full_like(r, float(ident)), r).int()
+
+
+def segment_reduce(x: torch.Tensor, offsets: torch.Tensor, op: str = "sum", out: torch.Tensor | None = None,
+                   validate: bool = False) -> torch.Tensor:
+    """[S] tensor of x's dtype: op (sum, min, max) over x.flatten()[offsets[j] : offsets[j+1]] for every j < S, S =
+    offsets.numel() - 1: torch.segment_reduce(x, op, offsets=offsets) for float32 and int32 (rules above). x is
+    contiguous, offsets int32, 1-D, contiguous, on x's device, with 0 <= offsets[0] <= ... <= offsets[S] <= x.numel();
+    x.numel() + S < 2^31. An empty segment gives the identity (+0.0 / 0, +inf / INT32_MAX, -inf / INT32_MIN). out
+    (optional: 1-D, contiguous, x's dtype, at least S elements, not overlapping an input) is written in [:S] only and
+    returned as out[:S]. validate=True checks the offsets first (one host sync) and raises ValueError naming the first
+    offending entry; without it offsets that break the precondition give an unspecified result (nothing outside the
+    tensors is touched). S == 0 returns an empty tensor. Does not synchronise."""
+    s = _check_segments(x, offsets, op, "segment_reduce")
+    n = x.numel()
+    if out is not None:
+        if out.dtype != x.dtype:
+            raise TypeError(f"out must be {x.dtype}, got {out.dtype}")
+        if out.device != x.device:
+            raise ValueError(f"out is on {out.device}, the input on {x.device}")
+        if out.dim() != 1 or not out.is_contiguous() or out.numel() < s:
+            raise ValueError(f"out must be 1-D, contiguous, with room for all {s} segments, got shape {tuple(out.shape)}")
+        if _overlap(out, x) or _overlap(out, offsets):
+            raise ValueError("out must not overlap x or offsets")
+    if validate:
+        _validate_offsets(offsets, n)
+    if x.is_cuda:
+        return ops().segment_reduce(x, offsets, OP_CODES[op], out)
+    r = _host_segment_reduce(x, offsets, op)
+    if out is None:
+        return r
+    out[:s] = r
+    return out[:s]
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if a.numel() == 0 or b.numel() == 0 or a.device != b.device:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def segment_scan(x: torch.Tensor, offsets: torch.Tensor, op: str = "sum", exclusive: bool = False,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """The running op (sum, min, max) inside every segment x.flatten()[offsets[j] : offsets[j+1]], with x's dtype and
+    shape: segmented_scan with a head at every offsets[j] < x.numel(), for callers who hold offsets and not head flags
+    (x, offsets and the limits as in segment_reduce; exclusive, out and the number rules as in segmented_scan). The
+    positions before offsets[0] form one run of their own, and so do the positions from offsets[S] on. There is no
+    validate: a head is stored only where 0 <= offsets[j] < x.numel(), so offsets out of order still touch nothing
+    outside the tensors. Does not synchronise."""
+    _check_segments(x, offsets, op, "segment_scan")
+    n = x.numel()
+    if x.is_cuda:
+        heads = ops().segment_heads(offsets, n, x)
+    else:
+        heads = torch.zeros(n, dtype=torch.uint8)
+        o = offsets.long()
+        heads[o[(o >= 0) & (o < n)]] = 1
+    return segmented_scan(x, heads, op, exclusive, out)
