@@ -47,16 +47,18 @@
 //    gives 1024 blocks, at least 16 TY rows; scan: the smallest that gives a column 65536 / ceil(inner / 4) chunks.
 // The association order of a float32 sum is what is written above: it depends on n, inner, the route and the chunk
 // only, never on the row's position, on outer or on timing. That is the "same bits" claim.
-#include <limits.h>
-#include <type_traits>
-
+// combine and Vec4 are seg_ops.h's; the identity (`ident`) is this file's own.
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "seg_ops.h"
 
 namespace {
+using pcmx::combine;  // seg_ops.h: int32 sums wrap; float min / max hand on a NaN from either side (torch's rule)
 using pcmx::kWave;
 using pcmx::lane_id;
 using pcmx::misaligned;
+using pcmx::ranges_overlap;
+using pcmx::Vec4;
 
 constexpr int kThreads = 256, kWaves = kThreads / kWave, kTile = kThreads * 4;
 constexpr int kGridCap = 2048;             // 256 CUs x 8 blocks, then grid-stride
@@ -64,27 +66,12 @@ constexpr long long kReduceFoldDirect = 4096;  // column partials reduced by one
 constexpr long long kScanFoldDirect = 1024;    // ... and scanned by one up to here
 constexpr long long kLimit = 1LL << 31;    // outer * n * inner must stay below
 
-template <class T> struct Vec4 { using type = pcmx::f32x4; };
-template <> struct Vec4<int> { using type = pcmx::i32x4; };
-
+// Not seg_ops.h's identity: a float sum starts from +0.0 here and from -0.0 there, which differ on a row of -0.0s.
 template <class T, int OP>
 __device__ __forceinline__ T ident() {
     if constexpr (OP == PCMX_OP_SUM) return T(0);
     else if constexpr (std::is_same<T, float>::value) return OP == PCMX_OP_MIN ? __builtin_inff() : -__builtin_inff();
     else return OP == PCMX_OP_MIN ? INT_MAX : INT_MIN;
-}
-
-// a op b. int32 sums wrap; float min / max hand on a NaN from either side (torch's rule).
-template <class T, int OP>
-__device__ __forceinline__ T comb(T a, T b) {
-    if constexpr (OP == PCMX_OP_SUM) {
-        if constexpr (std::is_same<T, int>::value) return (int)((unsigned)a + (unsigned)b);
-        else return a + b;
-    } else if constexpr (std::is_same<T, float>::value) {
-        return OP == PCMX_OP_MIN ? ((a < b || a != a) ? a : b) : ((a > b || a != a) ? a : b);
-    } else {
-        return OP == PCMX_OP_MIN ? (a < b ? a : b) : (a > b ? a : b);
-    }
 }
 
 // elements e .. e + 3 of the `len` elements at p; the identity past the end
@@ -114,15 +101,15 @@ __device__ __forceinline__ void store4(T* p, long long e, long long len, bool ve
 
 template <class T, int OP>
 __device__ __forceinline__ T quad_fold(const T v[4]) {
-    return comb<T, OP>(comb<T, OP>(v[0], v[1]), comb<T, OP>(v[2], v[3]));
+    return combine<T, OP>(combine<T, OP>(v[0], v[1]), combine<T, OP>(v[2], v[3]));
 }
 
 // v becomes the running values of the quad; returns its total
 template <class T, int OP>
 __device__ __forceinline__ T quad_scan(T v[4]) {
-    v[1] = comb<T, OP>(v[0], v[1]);
-    v[2] = comb<T, OP>(v[1], v[2]);
-    v[3] = comb<T, OP>(v[2], v[3]);
+    v[1] = combine<T, OP>(v[0], v[1]);
+    v[2] = combine<T, OP>(v[1], v[2]);
+    v[3] = combine<T, OP>(v[2], v[3]);
     return v[3];
 }
 
@@ -132,10 +119,10 @@ __device__ __forceinline__ void quad_out(T base, const T r[4], bool exclusive, T
     if (exclusive) {
         o[0] = base;
 #pragma unroll
-        for (int k = 1; k < 4; ++k) o[k] = comb<T, OP>(base, r[k - 1]);
+        for (int k = 1; k < 4; ++k) o[k] = combine<T, OP>(base, r[k - 1]);
     } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = comb<T, OP>(base, r[k]);
+        for (int k = 0; k < 4; ++k) o[k] = combine<T, OP>(base, r[k]);
     }
 }
 
@@ -144,7 +131,7 @@ template <class T, int OP>
 __device__ __forceinline__ T group_scan(T s, int j, int G) {
     for (int off = 1; off < G; off <<= 1) {
         const T o = __shfl_up(s, off, kWave);
-        if (j >= off) s = comb<T, OP>(o, s);
+        if (j >= off) s = combine<T, OP>(o, s);
     }
     return s;
 }
@@ -164,9 +151,9 @@ __global__ __launch_bounds__(kThreads) void axis_group_reduce_kernel(const T* __
         for (long long i = 0; i < steps; ++i) {
             T v[4];
             load4(p, 4 * (j + G * i), len, vec != 0, id, v);
-            acc = comb<T, OP>(acc, quad_fold<T, OP>(v));
+            acc = combine<T, OP>(acc, quad_fold<T, OP>(v));
         }
-        for (int off = G >> 1; off > 0; off >>= 1) acc = comb<T, OP>(acc, __shfl_xor(acc, off, kWave));
+        for (int off = G >> 1; off > 0; off >>= 1) acc = combine<T, OP>(acc, __shfl_xor(acc, off, kWave));
         if (j == 0 && row < rows) out[row] = acc;
     }
 }
@@ -190,9 +177,9 @@ __global__ __launch_bounds__(kThreads) void axis_group_scan_kernel(const T* x, T
             const T incl = group_scan<T, OP>(quad_scan<T, OP>(v), j, G);
             const T before = __shfl_up(incl, 1, kWave);
             const T total = __shfl(incl, (lane & ~(G - 1)) + G - 1, kWave);
-            quad_out<T, OP>(comb<T, OP>(carry, j ? before : id), v, exclusive != 0, o);
+            quad_out<T, OP>(combine<T, OP>(carry, j ? before : id), v, exclusive != 0, o);
             store4(q, e, len, vec != 0, o);
-            carry = comb<T, OP>(carry, total);
+            carry = combine<T, OP>(carry, total);
         }
     }
 }
@@ -216,14 +203,14 @@ __global__ __launch_bounds__(kThreads) void axis_seg_reduce_kernel(const T* __re
         for (long long t = 0; t < tiles; ++t) {
             T v[4];
             load4(p, (t * kThreads + tid) * 4, len, vec != 0, id, v);
-            acc = comb<T, OP>(acc, quad_fold<T, OP>(v));
+            acc = combine<T, OP>(acc, quad_fold<T, OP>(v));
         }
 #pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) acc = comb<T, OP>(acc, __shfl_xor(acc, off, kWave));
+        for (int off = kWave / 2; off > 0; off >>= 1) acc = combine<T, OP>(acc, __shfl_xor(acc, off, kWave));
         if (lane == 0) s_w[buf][wave] = acc;
         __syncthreads();
         if (tid == 0)
-            out[s] = comb<T, OP>(comb<T, OP>(s_w[buf][0], s_w[buf][1]), comb<T, OP>(s_w[buf][2], s_w[buf][3]));
+            out[s] = combine<T, OP>(combine<T, OP>(s_w[buf][0], s_w[buf][1]), combine<T, OP>(s_w[buf][2], s_w[buf][3]));
     }
 }
 
@@ -254,12 +241,12 @@ __global__ __launch_bounds__(kThreads) void axis_seg_scan_kernel(const T* x, T* 
 #pragma unroll
             for (int w = 1; w < kWaves; ++w) {
                 if (w == wave) waves_before = total;
-                total = comb<T, OP>(total, s_w[buf][w]);
+                total = combine<T, OP>(total, s_w[buf][w]);
             }
-            const T base = comb<T, OP>(comb<T, OP>(carry, waves_before), lane ? before : id);
+            const T base = combine<T, OP>(combine<T, OP>(carry, waves_before), lane ? before : id);
             quad_out<T, OP>(base, v, exclusive != 0, o);
             store4(q, e, len, vec != 0, o);
-            carry = comb<T, OP>(carry, total);
+            carry = combine<T, OP>(carry, total);
         }
     }
 }
@@ -289,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void axis_col_reduce_kernel(const T* __re
             T v[4];
             load4(p, col, inner, vec != 0, id, v);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = comb<T, OP>(acc[k], v[k]);
+            for (int k = 0; k < 4; ++k) acc[k] = combine<T, OP>(acc[k], v[k]);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) s_p[k][tid] = acc[k];
@@ -297,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void axis_col_reduce_kernel(const T* __re
         for (int h = TY >> 1; h > 0; h >>= 1) {
             if (ty < h) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) s_p[k][tid] = comb<T, OP>(s_p[k][tid], s_p[k][tid + h * TX]);
+                for (int k = 0; k < 4; ++k) s_p[k][tid] = combine<T, OP>(s_p[k][tid], s_p[k][tid + h * TX]);
             }
             __syncthreads();
         }
@@ -328,7 +315,7 @@ __global__ __launch_bounds__(kThreads) void axis_col_scan_kernel(const T* x, T* 
             T v[4], nxt[4];
             load4(p, col, inner, vec != 0, id, v);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) nxt[k] = comb<T, OP>(acc[k], v[k]);
+            for (int k = 0; k < 4; ++k) nxt[k] = combine<T, OP>(acc[k], v[k]);
             store4(q, col, inner, vec != 0, exclusive ? acc : nxt);
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = nxt[k];
@@ -414,11 +401,6 @@ int check_extents(long long outer, long long n, long long inner, long long* tota
         return PCMX_ERR_ARG;
     *total = outer * n * inner;
     return 0;
-}
-
-bool overlap(const void* a, size_t ab, const void* b, size_t bb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bb && b0 < a0 + ab;
 }
 
 template <class T, int OP>
@@ -510,7 +492,7 @@ int axis_reduce(const T* x, T* out, long long outer, long long n, long long inne
     if (op < PCMX_OP_SUM || op > PCMX_OP_MAX || check_extents(outer, n, inner, &total)) return PCMX_ERR_ARG;
     if (route < 0 || route > PCMX_AXIS_COLUMN_SPLIT || chunk < 0) return PCMX_ERR_ARG;
     const size_t out_b = (size_t)outer * inner * sizeof(T);
-    if (out_b && overlap(out, out_b, x, total ? (size_t)total * sizeof(T) : 1)) return PCMX_ERR_ARG;
+    if (ranges_overlap(out, out_b, x, total ? (size_t)total * sizeof(T) : 1)) return PCMX_ERR_ARG;
     if (outer == 0 || inner == 0) return 0;
     if (n == 0) {
         if (op == PCMX_OP_SUM) PCMX_HIP_RET(hipMemsetAsync(out, 0, out_b, s));
@@ -532,7 +514,7 @@ int axis_scan(const T* x, T* out, long long outer, long long n, long long inner,
     if (!x || !out || misaligned(x) || misaligned(out) || misaligned(workspace)) return PCMX_ERR_ARG;
     if (op < PCMX_OP_SUM || op > PCMX_OP_MAX || check_extents(outer, n, inner, &total)) return PCMX_ERR_ARG;
     if (route < 0 || route > PCMX_AXIS_COLUMN_SPLIT || chunk < 0) return PCMX_ERR_ARG;
-    if (total && x != out && overlap(out, (size_t)total * sizeof(T), x, (size_t)total * sizeof(T))) return PCMX_ERR_ARG;
+    if (x != out && ranges_overlap(out, (size_t)total * sizeof(T), x, (size_t)total * sizeof(T))) return PCMX_ERR_ARG;
     if (total == 0) return 0;
     Plan pl;
     if (const int rc = make_plan(kScan, outer, n, inner, route, chunk, &pl)) return rc;

@@ -2,7 +2,8 @@
 // j < S, for float32 / int32 and sum / min / max; and the head flags of the same offsets for the segmented scan of
 // scanbykey.hip. Merge-based segmented reduction (Merrill, Garland, "Merge-based parallel sparse matrix-vector
 // multiplication", SC16) on the merge-path partition of merge.hip and the carry scheme of scanbykey.hip. No counterpart
-// in the reference programs.
+// in the reference programs. The operator (identity, combine) and the wave scan of (flag, value) pairs that both carry
+// schemes use are seg_ops.h's.
 //
 // With base = offsets[0], ends e_j = offsets[j+1] - base (j < S) and m = e_{S-1}, the list of ends is merged with the
 // natural numbers 0 .. m-1: a path of m + S steps on which end j sits at position e_j + j and element i behind every
@@ -42,17 +43,18 @@
 // 1.75 ms at length 100, 90 ms at one segment, FASTER at 2684 segments of 10^5 (0.196 against 0.378 ms).
 // kThreads x kItems = 256 x 17 is merge.hip's tile (odd item count: the lanes' private LDS positions spread over the
 // banks); the tile, the item count and kCarryThreads are starting values, NOT MEASURED against alternatives.
-#include <limits.h>
-
-#include <type_traits>
-
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "seg_ops.h"
 
 namespace {
+using pcmx::combine;
+using pcmx::identity;
 using pcmx::kWave;
 using pcmx::misaligned;
 using pcmx::pad4;
+using pcmx::ranges_overlap;
+using pcmx::Vec4;
 
 constexpr int kThreads = 256;
 constexpr int kItems = 17;                // path steps per lane (odd: see above)
@@ -60,37 +62,6 @@ constexpr int kTile = kThreads * kItems;  // 4352 path steps per block
 constexpr int kWaves = kThreads / kWave;
 constexpr int kCarryThreads = 1024;
 constexpr long long kMaxPath = (1LL << 31) - 1;
-
-template <class T, int OP>
-__device__ __forceinline__ T identity() {
-    if constexpr (std::is_same<T, float>::value)
-        return OP == PCMX_OP_SUM ? -0.0f : (OP == PCMX_OP_MIN ? __builtin_inff() : -__builtin_inff());
-    else
-        return OP == PCMX_OP_SUM ? 0 : (OP == PCMX_OP_MIN ? INT_MAX : INT_MIN);
-}
-
-// what an empty segment gets: the identity, with +0.0 for a float sum
-template <class T, int OP>
-__device__ __forceinline__ T empty_value() {
-    if constexpr (std::is_same<T, float>::value && OP == PCMX_OP_SUM)
-        return 0.0f;
-    else
-        return identity<T, OP>();
-}
-
-// a OP b; int32 sums wrap, float min / max hand on a NaN operand
-template <class T, int OP>
-__device__ __forceinline__ T combine(T a, T b) {
-    if constexpr (std::is_same<T, float>::value) {
-        if constexpr (OP == PCMX_OP_SUM) return a + b;
-        if constexpr (OP == PCMX_OP_MIN) return (a < b || a != a) ? a : b;
-        return (a > b || a != a) ? a : b;
-    } else {
-        if constexpr (OP == PCMX_OP_SUM) return (int)((unsigned)a + (unsigned)b);
-        if constexpr (OP == PCMX_OP_MIN) return a < b ? a : b;
-        return a > b ? a : b;
-    }
-}
 
 // base = offsets[0] forced into [0, n] and m = offsets[S] - base forced into [0, n - base]: whatever the offsets hold,
 // base + m <= n, so a value index base + v with v < m is inside x[0, n).
@@ -246,6 +217,11 @@ __global__ __launch_bounds__(kThreads) void tile_kernel(const T* __restrict__ x,
     }
     // ---- segmented scan over the lanes in a fixed order: a lane's item is (closed an end, its tail) under
     // (f1, v1) . (f2, v2) = (f1 | f2, f2 ? v2 : v1 OP v2)
+    // (seg_ops.h's wave_scan_pairs / pair_of_lanes_below, kept written out in this kernel: with the two calls the
+    // registers and spills stay equal but the schedule moves (4-5 s_nop fewer in four of the six kernels, one s_xor_b64
+    // more in the other two), and the float32 sum over power-law rows of mean length 100 at 2^28 elements measured
+    // 0.432-0.436 against 0.428-0.431 ms, and 0.427 against 0.426 ms with the run order swapped. carry_kernel below
+    // takes the calls.)
     unsigned f = first != ~0u ? 1u : 0u;
     T a = acc;
 #pragma unroll
@@ -280,7 +256,7 @@ __global__ __launch_bounds__(kThreads) void tile_kernel(const T* __restrict__ x,
 
     // ---- coalesced stores: every end of the tile was consumed by exactly one lane when the offsets are in order;
     // when they are not, a word of s_out may be stale, which is an unspecified result and no fault
-    const T ev0 = empty_value<T, OP>();
+    const T ev0 = pcmx::positive_zero_identity<T, OP>();  // what an empty segment gets
 #pragma unroll
     for (int k = 0; k < kItems; ++k) {
         const unsigned i = tid + (unsigned)k * kThreads;
@@ -295,11 +271,6 @@ __global__ __launch_bounds__(kThreads) void tile_kernel(const T* __restrict__ x,
 // wave by shuffles and over the waves through LDS, and `run`, the open partial on entry to the round, is carried in a
 // register. The order is fixed by the tile numbers alone. The arrays are padded to a multiple of 4 entries, so the
 // vector accesses stay inside the workspace; entries from ntiles on are masked to the neutral element.
-template <class T>
-struct Vec4 {
-    typedef T type __attribute__((ext_vector_type(4)));
-};
-
 template <class T, int OP>
 __global__ __launch_bounds__(kCarryThreads) void carry_kernel(const unsigned* __restrict__ flag, const T* __restrict__ open,
                                                               T* __restrict__ carry, int ntiles) {
@@ -332,25 +303,14 @@ __global__ __launch_bounds__(kCarryThreads) void carry_kernel(const unsigned* __
             v = f4[j] ? v4[j] : combine<T, OP>(v, v4[j]);
             f |= f4[j];
         }
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const T ov = __shfl_up(v, off, kWave);
-            const unsigned of = __shfl_up(f, off, kWave);
-            if (lane >= off) {
-                v = f ? v : combine<T, OP>(ov, v);
-                f |= of;
-            }
-        }
+        pcmx::wave_scan_pairs<T, OP>(f, v);
         if (lane == kWave - 1) {
             s_v[r & 1][wave] = v;
             s_f[r & 1][wave] = f;
         }
-        T ev = __shfl_up(v, 1, kWave);  // the pair of the threads below this one in the wave
-        unsigned ef = __shfl_up(f, 1, kWave);
-        if (lane == 0) {
-            ev = id;
-            ef = 0u;
-        }
+        T ev;  // the pair of the threads below this one in the wave
+        unsigned ef;
+        pcmx::pair_of_lanes_below<T, OP>(f, v, ef, ev);
         __syncthreads();
         T pv = run, total = run;
 #pragma unroll
@@ -418,12 +378,6 @@ int launch_op(const T* x, long long n, const int* offsets, long long S, T* out, 
     return (int)hipGetLastError();
 }
 
-// two ranges of 4-byte elements share a byte
-inline bool overlap(const void* a, long long na, const void* b, long long nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return na > 0 && nb > 0 && a0 < b0 + (uintptr_t)nb * 4 && b0 < a0 + (uintptr_t)na * 4;
-}
-
 template <class T>
 int launch(const T* x, long long n, const int32_t* offsets, long long S, int op, T* out, void* workspace, hipStream_t s) {
     if (op < PCMX_OP_SUM || op > PCMX_OP_MAX) return PCMX_ERR_ARG;
@@ -431,7 +385,9 @@ int launch(const T* x, long long n, const int32_t* offsets, long long S, int op,
     if (!offsets || misaligned(offsets, 3u)) return PCMX_ERR_ARG;
     if (S == 0) return 0;
     if ((n && (!x || misaligned(x, 3u))) || !out || misaligned(out) || !workspace || misaligned(workspace)) return PCMX_ERR_ARG;
-    if (overlap(out, S, x, n) || overlap(out, S, offsets, S + 1)) return PCMX_ERR_ARG;
+    const size_t out_b = (size_t)S * 4;  // 4-byte elements throughout
+    if (ranges_overlap(out, out_b, x, (size_t)n * 4) || ranges_overlap(out, out_b, offsets, (size_t)(S + 1) * 4))
+        return PCMX_ERR_ARG;
     switch (op) {
         case PCMX_OP_SUM: return launch_op<T, PCMX_OP_SUM>(x, n, offsets, S, out, workspace, s);
         case PCMX_OP_MIN: return launch_op<T, PCMX_OP_MIN>(x, n, offsets, S, out, workspace, s);

@@ -8,9 +8,11 @@
 // bitwise reproducible run to run (no float atomics, cdna_hip_programming.md G12). Grid cap (round 4,
 // scripts/stream_bw_lab.hip, profiles/r4_bench/stream_bw_lab.txt): a 1e9-f32 read stream runs 6.70 TB/s with 2048
 // blocks of 4 float4 per lane and 7.14 TB/s with 16384 (more blocks retire and refill the CUs' queues between
-// each other's HBM round trips).
+// each other's HBM round trips). Vec4 is seg_ops.h's; the operator below is this file's own (a sum starts from +0.0 and
+// min / max do not hand on a NaN), so that header's identity / combine are not used here.
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "seg_ops.h"
 
 namespace {
 using pcmx::kWave;
@@ -18,16 +20,7 @@ constexpr int kThreads = 256;
 constexpr int kUnroll = 4;  // float4 loads in flight per lane: 4 x 16 B x 256 threads = 16 KiB per block
 constexpr int kMaxBlocks = 16384;
 
-template <class T>
-struct Vec4;
-template <>
-struct Vec4<float> {
-    using type = pcmx::f32x4;
-};
-template <>
-struct Vec4<int32_t> {
-    using type = pcmx::i32x4;
-};
+using pcmx::Vec4;
 
 template <class T, int OP>
 __device__ __forceinline__ T identity() {

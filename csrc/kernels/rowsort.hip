@@ -10,40 +10,40 @@
 //    G = 1 is the wave-per-row sort of short rows (4 rows per 256-thread block), G = 8 the block-per-row sort up to
 //    sort.hip's 16384-key tile; the host takes the smallest R that holds the row. The row is loaded once in (wave, row,
 //    lane) order, transformed, and runs ceil(bits / 8) least-significant-digit passes without leaving the CU: ranks by
-//    match-any ballots on the wave's 256 LDS counters exactly as in sort.hip, the counters of the group's waves summed
-//    and scanned by the group, the keys (and a payload) scattered through LDS and read back in (wave, row, lane) order.
+//    match-any ballots on the wave's 256 LDS counters exactly as sort.hip's (radix_rank.h's rank_row, written out here;
+//    cnt_load / cnt_store are that header's), the counters of the group's waves summed and scanned by the group, the
+//    keys (and a payload) scattered through LDS and read back in (wave, row, lane) order.
 //    After the last pass the first `keep` entries stream out of LDS with the transform inverted.
 //  * Every access to global memory is a 4-byte access at lane-consecutive addresses: row r starts at byte 4 r cols,
 //    which is 16-byte aligned only when cols % 4 == 0, and nothing before a row's first key or past its last is touched.
 //  * A group without a row (the last block of a `rows` that does not divide) and the waves past the end of a short row
 //    run the same passes on zero valid keys: every thread of the block reaches every barrier.
 //  * row_select_kernel<GATHER>: one 512-thread block per row. Four most-significant-digit histogram passes over the row
-//    (256 LDS counters, the digit chosen in the block) give the k-th key T and need_eq, the number of ties to take. For
-//    top-k one more sweep in position order follows, 512 keys per step, carrying two running counts (better than T,
-//    equal to T) from step to step: the k survivors leave in ascending position, values canonical, positions int32.
-//    The sweep stops at the step that stores the k-th survivor. Counters, threshold and counts are per block = per row.
+//    (256 LDS counters, the digit chosen in the block behind radix_rank.h's block_excl256) give the k-th key T and
+//    need_eq, the number of ties to take. For top-k one more sweep in position order follows, 512 keys per step,
+//    carrying two running counts (better than T, equal to T) from step to step: the k survivors leave in ascending
+//    position, values canonical, positions int32. The sweep stops at the step that stores the k-th survivor. Counters,
+//    threshold and counts are per block = per row.
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
 #include "radix_key.h"
+#include "radix_rank.h"
 
 namespace {
+using pcmx::block_excl256;
+using pcmx::cnt_load;
+using pcmx::cnt_store;
 using pcmx::from_key;
 using pcmx::kWave;
 using pcmx::lanes_below;
 using pcmx::misaligned;
+using pcmx::ranges_overlap;
 using pcmx::to_key;
 
 constexpr int kDigits = 256;
 constexpr int kWaveRowWaves = 4;   // wave-per-row: 4 rows per 256-thread block
 constexpr int kBlockRowWaves = 8;  // block-per-row: 512 threads
 constexpr long long kMaxN = (1LL << 30) - 1;  // the family's limit on rows * cols (int32 positions, 30-bit counts)
-
-__device__ __forceinline__ unsigned cnt_load(const unsigned* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ void cnt_store(unsigned* p, unsigned v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
 
 struct RowSortArgs {
     unsigned rows, cols, keep;
@@ -89,6 +89,9 @@ __global__ __launch_bounds__(NW * kWave) void row_sort_kernel(const unsigned* __
         for (int r = 0; r < R; ++r) {
             const bool valid = i0 + (unsigned)(r * kWave) < n;
             const unsigned d = (key[r] >> shift) & mask;
+            // radix_rank.h's rank_row, kept written out: as a call (counters by pointer or by array reference, the
+            // counter read before or after the ballots) the compiler orders the row's ballots differently and the four
+            // R == 1 kernels grow by 5-7 VGPRs (34 -> 39, 36 -> 42, 40 -> 45, 40 -> 46)
             const unsigned long long vmask = __ballot(valid);
             unsigned plo = (unsigned)vmask, phi = (unsigned)(vmask >> 32);
 #pragma unroll
@@ -185,23 +188,6 @@ struct RowSelArgs {
     unsigned flip;
 };
 
-// Exclusive prefix of v over threads 0 .. 255 (sort.hip's block_excl256): every thread calls it, one barrier inside.
-__device__ __forceinline__ unsigned excl256(unsigned v, unsigned* s_wsum) {
-    const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-    unsigned inc = v;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const unsigned o = __shfl_up(inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (wave < 4 && lane == kWave - 1) s_wsum[wave] = inc;
-    __syncthreads();
-    unsigned add = 0u;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) add += w < wave ? s_wsum[w] : 0u;
-    return inc - v + add;
-}
-
 template <bool GATHER>
 __global__ __launch_bounds__(kSelThreads) void row_select_kernel(const unsigned* __restrict__ x, unsigned* __restrict__ out_vals,
                                                                  unsigned* __restrict__ out_idx, const RowSelArgs a) {
@@ -239,7 +225,7 @@ __global__ __launch_bounds__(kSelThreads) void row_select_kernel(const unsigned*
         }
         __syncthreads();
         const unsigned c = tid < kDigits ? s_h[tid] : 0u;
-        const unsigned excl = excl256(c, s_wsum);
+        const unsigned excl = block_excl256(c, s_wsum);
         if (tid < kDigits && excl < k_rem && k_rem <= excl + c) {  // exactly one bin
             s_state[0] = prefix | ((unsigned)tid << shift);
             s_state[1] = k_rem - excl;
@@ -283,12 +269,6 @@ __global__ __launch_bounds__(kSelThreads) void row_select_kernel(const unsigned*
     }
 }
 
-// [p, p + pb) and [q, q + qb) share a byte
-inline bool overlap(const void* p, size_t pb, const void* q, size_t qb) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return p && q && pb && qb && a < b + qb && b < a + pb;
-}
-
 int check_shape(long long rows, long long cols) {
     if (rows < 0 || cols < 0) return PCMX_ERR_ARG;
     if (rows > 0 && cols > 0 && (rows > kMaxN || cols > kMaxN || rows * cols > kMaxN)) return PCMX_ERR_ARG;
@@ -312,9 +292,9 @@ extern "C" int pcmx_row_sort_b32(const void* keys_in, void* keys_out, const void
     if (mode != PCMX_SORT_KEYS && (!vals_out || misaligned(vals_out))) return PCMX_ERR_ARG;
     const size_t in_b = (size_t)rows * cols * 4u, out_b = (size_t)rows * keep * 4u;
     const bool pairs = mode == PCMX_SORT_PAIRS, has_v = mode != PCMX_SORT_KEYS;
-    if (overlap(keys_out, out_b, keys_in, in_b) || (has_v && overlap(vals_out, out_b, keys_in, in_b)) ||
-        (pairs && (overlap(keys_out, out_b, vals_in, in_b) || overlap(vals_out, out_b, vals_in, in_b))) ||
-        (has_v && overlap(keys_out, out_b, vals_out, out_b)))
+    if (ranges_overlap(keys_out, out_b, keys_in, in_b) || (has_v && ranges_overlap(vals_out, out_b, keys_in, in_b)) ||
+        (pairs && (ranges_overlap(keys_out, out_b, vals_in, in_b) || ranges_overlap(vals_out, out_b, vals_in, in_b))) ||
+        (has_v && ranges_overlap(keys_out, out_b, vals_out, out_b)))
         return PCMX_ERR_ARG;
     if (rows == 0 || cols == 0 || keep == 0) return 0;
     RowSortArgs a;
@@ -357,7 +337,8 @@ extern "C" int pcmx_row_topk_b32(const void* keys, long long rows, long long col
     if (const int rc = check_select(keys, rows, cols, k, key_type)) return rc;
     if (!out_vals || misaligned(out_vals) || !out_idx || misaligned(out_idx)) return PCMX_ERR_ARG;
     const size_t in_b = (size_t)rows * cols * 4u, out_b = (size_t)rows * k * 4u;
-    if (overlap(out_vals, out_b, keys, in_b) || overlap(out_idx, out_b, keys, in_b) || overlap(out_vals, out_b, out_idx, out_b))
+    if (ranges_overlap(out_vals, out_b, keys, in_b) || ranges_overlap(out_idx, out_b, keys, in_b) ||
+        ranges_overlap(out_vals, out_b, out_idx, out_b))
         return PCMX_ERR_ARG;
     if (rows == 0 || cols == 0 || k == 0) return 0;
     RowSelArgs a;
@@ -373,7 +354,7 @@ extern "C" int pcmx_row_kth_key_b32(const void* keys, long long rows, long long 
                                     void* out, hipStream_t s) {
     if (const int rc = check_select(keys, rows, cols, k, key_type)) return rc;
     if (!out || misaligned(out)) return PCMX_ERR_ARG;
-    if (overlap(out, (size_t)rows * 4u, keys, (size_t)rows * cols * 4u)) return PCMX_ERR_ARG;
+    if (ranges_overlap(out, (size_t)rows * 4u, keys, (size_t)rows * cols * 4u)) return PCMX_ERR_ARG;
     if (rows == 0 || cols == 0 || k == 0) return 0;
     RowSelArgs a;
     a.rows = (unsigned)rows, a.cols = (unsigned)cols, a.k = (unsigned)k, a.key_type = key_type, a.flip = largest ? ~0u : 0u;

@@ -3,11 +3,12 @@
 // flags marks. The sibling of segreduce.hip, which writes one aggregate per run; this one writes every element. No
 // counterpart in the reference programs.
 //
-// Shared with segreduce.hip (the tile shape through tile_bits.h; the rest copied, the bodies differ): the persistent schedule
-// (one 512-thread block per CU, 32768-element tiles from an atomic ticket), the key and value loads, the head bits
-// from the neighbouring key bits (the lane's own row, DPP wave_shr:1, v_readlane of the previous row's lane 63, one
-// extra load per wave; the keys are read once) and the in-tile segmented scan in a fixed order (a lane's 4 elements,
-// 64 lanes by shuffles, 16 rows by a wave-uniform carry, 8 wave tails through LDS). What differs:
+// Shared with segreduce.hip through tile_bits.h: the tile shape, the key and value loads, the head bits from the
+// neighbouring key bits (the lane's own row, DPP wave_shr:1, v_readlane of the previous row's lane 63, one extra load per
+// wave; the keys are read once) and the fold of the 8 wave tails; the operator is seg_ops.h's. Also the same, but
+// written out in both files: the persistent schedule (one 512-thread block per CU, 32768-element tiles from an atomic
+// ticket) and the per-row wave scan (a lane's 4 elements, 64 lanes by shuffles, 16 rows by a wave-uniform carry). What
+// differs:
 //  * Nothing is compacted, so no output position depends on another tile: there is NO look-back. No block ever waits
 //    for another block: no spin loop, no status granule, no timeout word, and nothing to report afterwards.
 //  * Values never travel between blocks while they run (a float carried through a look-back would make the result
@@ -31,66 +32,29 @@
 // gathered base: 8.9 / 5.9 / 4.9 / 4.8 / 4.7), run positions 0.50 / 0.51 / 0.50 / 0.87 / 0.92 ms (8.5 / 6.0 / 5.3 / 5.3 /
 // 5.2); 1.26-1.30x the time of a copy of the same bytes while runs are shorter than a tile, 2.1x with all keys equal,
 // where the lead kernel takes 0.39 of 1.0 ms. The carry kernel takes 0.020 ms.
-#include <limits.h>
-
-#include <type_traits>
-
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "seg_ops.h"
 #include "tile_bits.h"
 
 namespace {
+using pcmx::combine;
 using pcmx::device_cus;
 using pcmx::from_lane_below;
+using pcmx::identity;
 using pcmx::kWave;
 using pcmx::misaligned;
 using pcmx::pad4;
 using pcmx::u32x4;
+using pcmx::Vec4;
 using namespace pcmx::tile_bits;         // the tile shape
 constexpr unsigned kHasHead = 1u << 31;  // tile_meta: the tile holds a run head; low bits: lead length
-enum { kSrcOne = 0, kSrcI32 = 1, kSrcF32 = 2 };
 
 struct SbkWs {
     unsigned ticket;  // zeroed before every launch
     unsigned pad[3];
     // followed by unsigned tile_meta[tiles4], 4-byte tile_closing[tiles4], 4-byte tile_carry[tiles4]
     // (tiles4 = tiles padded to a multiple of 4); every entry below `tiles` is written before it is read
-};
-
-template <class T, int OP>
-__device__ __forceinline__ T identity() {
-    if constexpr (std::is_same<T, float>::value)
-        return OP == PCMX_OP_SUM ? -0.0f : (OP == PCMX_OP_MIN ? __builtin_inff() : -__builtin_inff());
-    else
-        return OP == PCMX_OP_SUM ? 0 : (OP == PCMX_OP_MIN ? INT_MAX : INT_MIN);
-}
-
-// what the first element of a run gets in exclusive mode: the identity, with +0.0 for a float sum
-template <class T, int OP>
-__device__ __forceinline__ T head_value() {
-    if constexpr (std::is_same<T, float>::value && OP == PCMX_OP_SUM)
-        return 0.0f;
-    else
-        return identity<T, OP>();
-}
-
-// a OP b; int32 sums wrap, float min / max hand on a NaN operand
-template <class T, int OP>
-__device__ __forceinline__ T combine(T a, T b) {
-    if constexpr (std::is_same<T, float>::value) {
-        if constexpr (OP == PCMX_OP_SUM) return a + b;
-        if constexpr (OP == PCMX_OP_MIN) return (a < b || a != a) ? a : b;
-        return (a > b || a != a) ? a : b;
-    } else {
-        if constexpr (OP == PCMX_OP_SUM) return (int)((unsigned)a + (unsigned)b);
-        if constexpr (OP == PCMX_OP_MIN) return a < b ? a : b;
-        return a > b ? a : b;
-    }
-}
-
-template <class T>
-struct Vec4 {
-    typedef T type __attribute__((ext_vector_type(4)));
 };
 
 struct SideArrays {
@@ -127,39 +91,9 @@ __device__ __forceinline__ unsigned long long valid_bits(long long n, long long 
 // Head bits from the keys: bit 4r+j = element j of row r differs from its left neighbour (compared as bit patterns).
 // Keys at or past n are never read. Element 0 of the stream is a head: its neighbour is made to differ.
 __device__ __forceinline__ unsigned long long head_bits_from_keys(const unsigned* __restrict__ x, long long n, long long tile) {
-    const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-    const unsigned* xt = x + tile * kTileElems;
-    const unsigned off = (unsigned)(wave * kWaveItems + lane * 4);
-    const long long first = tile * kTileElems + (long long)wave * kWaveItems;  // wave-uniform
-    unsigned before = first == 0 ? ~x[0] : (first - 1 < n ? x[first - 1] : 0u);
-    u32x4 k[kRows];
-    if ((tile + 1) * kTileElems <= n) {  // block-uniform: full tiles take the branch-free path
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) k[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(xt + r * 256 + off));
-    } else {
-        const unsigned rem = (unsigned)(n - tile * kTileElems);  // the last, partial tile (once per launch)
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const unsigned e = off + r * 256;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (e + 0 < rem) v.x = xt[e + 0];
-            if (e + 1 < rem) v.y = xt[e + 1];
-            if (e + 2 < rem) v.z = xt[e + 2];
-            if (e + 3 < rem) v.w = xt[e + 3];
-            k[r] = v;
-        }
-    }
-    unsigned long long bits = 0ull;
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const u32x4 q = k[r];
-        const unsigned below = from_lane_below(q.w);
-        const unsigned p = lane == 0 ? before : below;
-        const unsigned h = (q.x != p ? 1u : 0u) | (q.y != q.x ? 2u : 0u) | (q.z != q.y ? 4u : 0u) | (q.w != q.z ? 8u : 0u);
-        bits |= (unsigned long long)h << (4 * r);
-        before = (unsigned)__builtin_amdgcn_readlane((int)q.w, 63);
-    }
-    return bits & valid_bits(n, tile);
+    TileKeys t;  // dropped again: only the bits are kept
+    load_keys(x, n, tile, t);
+    return head_bits(t) & valid_bits(n, tile);
 }
 
 // Head bits from a byte stream of flags (4-byte aligned): a non-zero byte starts a run, and so does element 0.
@@ -194,48 +128,6 @@ __device__ __forceinline__ unsigned long long head_bits_from_flags(const unsigne
     return bits;
 }
 
-// The tile's values; elements at or past n are never read and take the op's identity (0 for the constant-1 source:
-// the tile's closing aggregate must not count them).
-template <int SRC, class T, int OP>
-__device__ __forceinline__ void load_vals(const T* __restrict__ vals, long long n, long long tile,
-                                          typename Vec4<T>::type (&v)[kRows]) {
-    typedef typename Vec4<T>::type V;
-    const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-    if constexpr (SRC == kSrcOne) {
-        if ((tile + 1) * kTileElems <= n) {  // block-uniform
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) v[r] = V{1, 1, 1, 1};
-            return;
-        }
-        const long long base = tile * kTileElems + wave * kWaveItems + lane * 4;
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const long long e = base + r * 256;
-            v[r] = V{e + 0 < n ? 1 : 0, e + 1 < n ? 1 : 0, e + 2 < n ? 1 : 0, e + 3 < n ? 1 : 0};
-        }
-    } else {
-        const T* vt = vals + tile * kTileElems;
-        const unsigned off = (unsigned)(wave * kWaveItems + lane * 4);
-        if ((tile + 1) * kTileElems <= n) {
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) v[r] = __builtin_nontemporal_load(reinterpret_cast<const V*>(vt + r * 256 + off));
-            return;
-        }
-        const unsigned rem = (unsigned)(n - tile * kTileElems);
-        const T id = identity<T, OP>();
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const unsigned e = off + r * 256;
-            V q = {id, id, id, id};
-            if (e + 0 < rem) q.x = vt[e + 0];
-            if (e + 1 < rem) q.y = vt[e + 1];
-            if (e + 2 < rem) q.z = vt[e + 2];
-            if (e + 3 < rem) q.w = vt[e + 3];
-            v[r] = q;
-        }
-    }
-}
-
 // One tile: loads its head bits and values (all of them before the first store: out may be the value stream), scans
 // it with the identity as carry-in, writes every output below n and the tile's summary. Returns with the next ticket
 // in *s_next.
@@ -246,7 +138,7 @@ __device__ __forceinline__ void process_tile(const void* __restrict__ keys_or_he
     typedef typename Vec4<T>::type V;
     const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
     const T id = identity<T, OP>();
-    const T hv = head_value<T, OP>();
+    const T hv = pcmx::positive_zero_identity<T, OP>();  // what a run's first element gets in exclusive mode
     V v[kRows];
     unsigned long long bits;
     if constexpr (FLAGS)
@@ -259,6 +151,8 @@ __device__ __forceinline__ void process_tile(const void* __restrict__ keys_or_he
     // ---- segmented scan, wave-local, in input order: per row the lane's 4 elements serially, then the 64 lanes by
     //      shuffles; rcur carries the open run's aggregate from row to row. v[r] becomes the row's outputs, still
     //      without what the earlier waves hold of the run that is open at this wave's first element.
+    //      (The row's wave scan up to `acc` is segreduce.hip's text; shared as a function it moves both kernels'
+    //      registers and spills, see the comment there.)
     T rcur = id;
     int first = kWaveItems;  // wave-uniform: the wave's first head, in elements from the wave's start
 #pragma unroll
@@ -302,15 +196,13 @@ __device__ __forceinline__ void process_tile(const void* __restrict__ keys_or_he
     }
     __syncthreads();
     // ---- the open run's aggregate on entry to this wave and on leaving the tile, and the tile's first head
-    T wc = id, closing = id;
-    int lead = -1;
+    T wc, closing;
+    fold_wave_tails<T, OP>(s_tail, [&](int w) { return s_first[w] < kWaveItems; }, wc, closing);
+    int lead = -1;  // the tile's first head: that of the lowest wave with one
 #pragma unroll
     for (int w = 0; w < kWaves; ++w) {
-        if (w == wave) wc = closing;
-        const T tw = s_tail[w];
         const int fw = s_first[w];
         if (lead < 0 && fw < kWaveItems) lead = w * kWaveItems + fw;
-        closing = fw < kWaveItems ? tw : combine<T, OP>(closing, tw);
     }
     const bool full = (tile + 1) * kTileElems <= n;  // block-uniform
     const int valid = full ? kTileElems : (int)(n - tile * kTileElems);
@@ -389,26 +281,15 @@ __global__ __launch_bounds__(kCarryThreads) void scanbykey_carry_kernel(const un
         v = h ? tile_closing[t] : combine<T, OP>(v, tile_closing[t]);
         f |= h ? 1u : 0u;
     }
-    // inclusive scan of the pairs over the wave's 64 threads, then over the 8 waves
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const T ov = __shfl_up(v, off, kWave);
-        const unsigned of = __shfl_up(f, off, kWave);
-        if (lane >= off) {
-            v = f ? v : combine<T, OP>(ov, v);
-            f |= of;
-        }
-    }
+    // inclusive scan of the pairs over the wave's 64 threads (seg_ops.h), then over the 8 waves
+    pcmx::wave_scan_pairs<T, OP>(f, v);
     if (lane == kWave - 1) {
         s_v[wave] = v;
         s_f[wave] = f;
     }
-    T ev = __shfl_up(v, 1, kWave);  // the pair of the threads below this one in the wave
-    unsigned ef = __shfl_up(f, 1, kWave);
-    if (lane == 0) {
-        ev = id;
-        ef = 0u;
-    }
+    T ev;  // the pair of the threads below this one in the wave
+    unsigned ef;
+    pcmx::pair_of_lanes_below<T, OP>(f, v, ef, ev);
     __syncthreads();
     T pv = id;
     unsigned pf = 0u;

@@ -7,6 +7,8 @@
 // sticky error word, the header that pcmx_scan_check reads), hipMemsetAsync of the workspace per launch, and the
 // ballot / v_mbcnt lane offsets (tile_bits.h). The keep bit is the run head, key[i] != key[i-1] compared
 // as bit patterns; the look-back carries only the integer count of heads, so every output position is exact.
+// Shared with scanbykey.hip through tile_bits.h: the key and value loads of a tile, the head bits and the fold of the
+// wave tails; the operator (identity, combine) is seg_ops.h's.
 // What differs:
 //  * The neighbour key comes from the lane's own row (4 keys), the lane below (DPP wave_shr:1), the previous row's
 //    lane 63 (v_readlane) or, for a wave's first key, one extra load per wave; the keys are read once.
@@ -31,18 +33,19 @@
 // 0.60 / 0.60), float32 sum by key 1.02 / 0.87 / 0.77 / 0.74 / 0.77 ms (unique_consecutive + index_add_: 3.5 to 79 ms);
 // 1.5-3.5x the time of a copy of the same bytes (not bandwidth-bound). The fix-up kernel takes 0.106 ms for a run that
 // crosses all 8192 tiles.
-#include <limits.h>
-
-#include <type_traits>
-
 #include "lookback.h"
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
+#include "seg_ops.h"
 #include "tile_bits.h"
 
 namespace {
+using pcmx::combine;
+using pcmx::combine_rt;
 using pcmx::device_cus;
 using pcmx::from_lane_below;
+using pcmx::identity;
+using pcmx::identity_rt;
 using pcmx::kFlagAgg;
 using pcmx::kFlagIncl;
 using pcmx::kWave;
@@ -50,149 +53,17 @@ using pcmx::misaligned;
 using pcmx::pad2;
 using pcmx::pad4;
 using pcmx::u32x4;
+using pcmx::Vec4;
 using namespace pcmx::tile_bits;             // the tile shape (128 KiB of keys) and the per-element bit helpers
 constexpr unsigned kFirstIsHead = 1u << 31;  // tile_meta: the tile's first element starts a run
-enum { kSrcOne = 0, kSrcI32 = 1, kSrcF32 = 2 };
 
 // followed by unsigned long long status[tiles, padded to even], unsigned tile_p[tiles4], unsigned tile_meta[tiles4],
 // 4-byte tile_lead[tiles4] (tiles4 = tiles padded to a multiple of 4)
 typedef pcmx::LookbackHeader SegWs;
 typedef pcmx::GranuleU32 Granule;  // the tile's count of run heads
 
-template <class T, int OP>
-__device__ __forceinline__ T identity() {
-    if constexpr (std::is_same<T, float>::value)
-        return OP == PCMX_OP_SUM ? -0.0f : (OP == PCMX_OP_MIN ? __builtin_inff() : -__builtin_inff());
-    else
-        return OP == PCMX_OP_SUM ? 0 : (OP == PCMX_OP_MIN ? INT_MAX : INT_MIN);
-}
-
-// a OP b; int32 sums wrap, float min / max hand on a NaN operand
-template <class T, int OP>
-__device__ __forceinline__ T combine(T a, T b) {
-    if constexpr (std::is_same<T, float>::value) {
-        if constexpr (OP == PCMX_OP_SUM) return a + b;
-        if constexpr (OP == PCMX_OP_MIN) return (a < b || a != a) ? a : b;
-        return (a > b || a != a) ? a : b;
-    } else {
-        if constexpr (OP == PCMX_OP_SUM) return (int)((unsigned)a + (unsigned)b);
-        if constexpr (OP == PCMX_OP_MIN) return a < b ? a : b;
-        return a > b ? a : b;
-    }
-}
-
-template <class T>
-__device__ __forceinline__ T combine_rt(int op, T a, T b) {  // kernel-uniform op
-    return op == PCMX_OP_SUM ? combine<T, PCMX_OP_SUM>(a, b)
-                             : (op == PCMX_OP_MIN ? combine<T, PCMX_OP_MIN>(a, b) : combine<T, PCMX_OP_MAX>(a, b));
-}
-template <class T>
-__device__ __forceinline__ T identity_rt(int op) {
-    return op == PCMX_OP_SUM ? identity<T, PCMX_OP_SUM>()
-                             : (op == PCMX_OP_MIN ? identity<T, PCMX_OP_MIN>() : identity<T, PCMX_OP_MAX>());
-}
-
 __device__ __forceinline__ unsigned to_bits(float v) { return __float_as_uint(v); }
 __device__ __forceinline__ unsigned to_bits(int v) { return (unsigned)v; }
-
-// One tile's keys in registers, plus the key just before this wave's 4096 (the neighbour of its first key).
-struct TileKeys {
-    u32x4 k[kRows];
-    unsigned prev;
-};
-
-template <class T>
-struct Vec4 {
-    typedef T type __attribute__((ext_vector_type(4)));
-};
-
-// Keys at or past n are never read (they load as 0 and their head bits are dropped by head_bits' bound).
-__device__ __forceinline__ void load_keys(const unsigned* __restrict__ x, long long n, long long tile, TileKeys& t) {
-    const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-    const unsigned* xt = x + tile * kTileElems;
-    const unsigned off = (unsigned)(wave * kWaveItems + lane * 4);
-    const long long before = tile * kTileElems + (long long)wave * kWaveItems - 1;  // wave-uniform
-    // element 0 of the stream is a head: its neighbour is made to differ
-    t.prev = before < 0 ? ~x[0] : (before < n ? x[before] : 0u);
-    if ((tile + 1) * kTileElems <= n) {  // block-uniform: full tiles take the branch-free path
-#pragma unroll
-        for (int r = 0; r < kRows; ++r)
-            t.k[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(xt + r * 256 + off));
-        return;
-    }
-    const unsigned rem = (unsigned)(n - tile * kTileElems);  // the last, partial tile (once per launch)
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const unsigned e = off + r * 256;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (e + 0 < rem) v.x = xt[e + 0];
-        if (e + 1 < rem) v.y = xt[e + 1];
-        if (e + 2 < rem) v.z = xt[e + 2];
-        if (e + 3 < rem) v.w = xt[e + 3];
-        t.k[r] = v;
-    }
-}
-
-// The tile's values; elements at or past n are never read and take the op's identity.
-template <int SRC, class T, int OP>
-__device__ __forceinline__ void load_vals(const T* __restrict__ vals, long long n, long long tile,
-                                          typename Vec4<T>::type (&v)[kRows]) {
-    typedef typename Vec4<T>::type V;
-    if constexpr (SRC == kSrcOne) {
-        // run lengths: every element counts 1 (elements past n carry no head and close no run; the tile's closing
-        // aggregate must not count them)
-        const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-        if ((tile + 1) * kTileElems <= n) {  // block-uniform
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) v[r] = V{1, 1, 1, 1};
-            return;
-        }
-        const long long base = tile * kTileElems + wave * kWaveItems + lane * 4;
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const long long e = base + r * 256;
-            v[r] = V{e + 0 < n ? 1 : 0, e + 1 < n ? 1 : 0, e + 2 < n ? 1 : 0, e + 3 < n ? 1 : 0};
-        }
-    } else {
-        const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-        const T* vt = vals + tile * kTileElems;
-        const unsigned off = (unsigned)(wave * kWaveItems + lane * 4);
-        if ((tile + 1) * kTileElems <= n) {
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) v[r] = __builtin_nontemporal_load(reinterpret_cast<const V*>(vt + r * 256 + off));
-            return;
-        }
-        const unsigned rem = (unsigned)(n - tile * kTileElems);
-        const T id = identity<T, OP>();
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const unsigned e = off + r * 256;
-            V q = {id, id, id, id};
-            if (e + 0 < rem) q.x = vt[e + 0];
-            if (e + 1 < rem) q.y = vt[e + 1];
-            if (e + 2 < rem) q.z = vt[e + 2];
-            if (e + 3 < rem) q.w = vt[e + 3];
-            v[r] = q;
-        }
-    }
-}
-
-// Head bits of the lane's 64 elements: bit 4r+j = element j of row r starts a run (differs from its left neighbour).
-__device__ __forceinline__ unsigned long long head_bits(const TileKeys& t, long long n, long long tile) {
-    const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-    unsigned long long bits = 0ull;
-    unsigned before = t.prev;  // wave-uniform: the key left of this row's first
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const u32x4 k = t.k[r];
-        const unsigned below = from_lane_below(k.w);
-        const unsigned p = lane == 0 ? before : below;
-        const unsigned h = (k.x != p ? 1u : 0u) | (k.y != k.x ? 2u : 0u) | (k.z != k.y ? 4u : 0u) | (k.w != k.z ? 8u : 0u);
-        bits |= (unsigned long long)h << (4 * r);
-        before = (unsigned)__builtin_amdgcn_readlane((int)k.w, 63);
-    }
-    return drop_past_n(bits, n, tile);
-}
 
 // The side arrays behind the granules.
 struct SideArrays {
@@ -235,7 +106,7 @@ __device__ __forceinline__ void process_tile(const unsigned* __restrict__ keys, 
     load_keys(keys, n, tile, t);
     load_vals<SRC, T, OP>(vals, n, tile, v);
     // ---- head bits, then per row the integer wave prefix of the heads (input order: row, lane, element)
-    const unsigned long long bits = head_bits(t, n, tile);
+    const unsigned long long bits = drop_past_n(head_bits(t), n, tile);
     unsigned carry;  // wave-uniform: the wave's heads
     unsigned lane_off[kRows];
     rank_rows(bits, lane_off, carry);
@@ -267,6 +138,10 @@ __device__ __forceinline__ void process_tile(const unsigned* __restrict__ keys, 
     //      from row to row. A head closes the run before it and sends that run's aggregate to the stage at its in-tile
     //      rank. Only the wave's FIRST head closes a run that may reach into earlier waves: its aggregate waits in
     //      s_first for the wave tails.
+    //      (The row's wave scan up to `acc` has the same text in scanbykey.hip. As one __forceinline__ function of
+    //      tile_bits.h, returning acc / fmask / tail as a struct or through references, with the lane's 4 elements
+    //      inside or outside, it compiles differently: here 141 -> 143 SGPR spills in three kernels and 16 -> 0 bytes of
+    //      scratch in float min / max, there 129-169 -> 128-168 VGPRs and 68-116 -> 29-70 SGPR spills. Kept written out.)
     T rcur = id;
 #pragma unroll
     for (int r = 0; r < kRows; ++r) {
@@ -306,13 +181,8 @@ __device__ __forceinline__ void process_tile(const unsigned* __restrict__ keys, 
     if (lane == 0) s_tail[wave] = rcur;
     __syncthreads();
     // ---- the open run's aggregate on entry to this wave, and on leaving the tile
-    T wc = id, closing = id;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        if (w == wave) wc = closing;
-        const T tw = s_tail[w];
-        closing = s_wave_tot[w] ? tw : combine<T, OP>(closing, tw);
-    }
+    T wc, closing;
+    fold_wave_tails<T, OP>(s_tail, [&](int w) { return s_wave_tot[w] != 0u; }, wc, closing);
     if (agg == 0u) {  // block-uniform: no head, the whole tile is the lead of a run that began earlier
         if (threadIdx.x == 0) tile_lead[tile] = closing;
         return;

@@ -6,8 +6,9 @@
 //  * One 512-thread block per CU claims 64-KiB tiles (16384 keys) from the pass's atomic ticket in the workspace, so
 //    every predecessor of a claimed tile has itself been claimed by a resident block.
 //  * Tile order is (wave, row, lane): wave w owns keys [2048 w, 2048 (w + 1)) of the tile as 32 rows of 64 lanes. A row
-//    is ranked by match-any (one ballot per digit bit, v_mbcnt of the peer mask) on top of the wave's 256 LDS digit
-//    counters, so a key's rank counts exactly the equal digits before it in that order: the pass is stable.
+//    is ranked by match-any (radix_rank.h's rank_row: one ballot per digit bit, v_mbcnt of the peer mask) on top of the
+//    wave's 256 LDS digit counters, so a key's rank counts exactly the equal digits before it in that order: the pass
+//    is stable. cnt_load / cnt_store and block_excl256 are radix_rank.h's too, shared with rowsort.hip.
 //  * Thread d publishes digit d's granule of the tile: one 4-byte word {flag (2 bits), count (30 bits)}, one relaxed
 //    agent-scope store. Counts and prefixes stay below 2^30, which is why n is limited to 2^30 - 1.
 //  * The tile is scattered into LDS at its sorted positions and the NEXT tile's loads are issued (the registers of this
@@ -24,9 +25,12 @@
 #include "pcmx_common.h"
 #include "pcmx_hip.h"
 #include "radix_key.h"
+#include "radix_rank.h"
 
 namespace {
 using pcmx::align16;
+using pcmx::block_excl256;
+using pcmx::cnt_store;
 using pcmx::device_cus;
 using pcmx::from_key;
 using pcmx::kFlagAgg;
@@ -34,6 +38,7 @@ using pcmx::kFlagIncl;
 using pcmx::kSpinLimit;
 using pcmx::kWave;
 using pcmx::misaligned;
+using pcmx::rank_row;
 using pcmx::report_timeout;
 using pcmx::to_key;
 using pcmx::u32x4;
@@ -57,31 +62,6 @@ struct SortWs {
 static_assert(offsetof(SortWs, head) == 0 && offsetof(SortWs, pass_ticket) == 16 && offsetof(SortWs, hist) == 32 &&
                   sizeof(SortWs) == 32 + kMaxPasses * kDigits * 4,
               "the workspace layout is part of the C interface (pcmx_sort_workspace_bytes)");
-
-__device__ __forceinline__ unsigned cnt_load(const unsigned* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ void cnt_store(unsigned* p, unsigned v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-
-// Exclusive prefix of v over threads 0 .. 255 (waves 0 .. 3). Every thread of the block calls it (one barrier inside);
-// the result of threads 256 .. 511 is meaningless.
-__device__ __forceinline__ unsigned block_excl256(unsigned v, unsigned* s_wsum) {
-    const int lane = pcmx::lane_id(), wave = threadIdx.x / kWave;
-    unsigned inc = v;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const unsigned o = __shfl_up(inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (wave < 4 && lane == kWave - 1) s_wsum[wave] = inc;
-    __syncthreads();
-    unsigned add = 0u;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) add += w < wave ? s_wsum[w] : 0u;
-    return inc - v + add;
-}
 
 // ---------------------------------------------------------------- upfront histogram of every pass
 // Reads the keys once. LDS counters per block, then one global atomic add per non-empty bin and block. A wave whose 64
@@ -202,9 +182,6 @@ __global__ __launch_bounds__(kThreads) void sort_pass_kernel(const unsigned* __r
     if (cur >= a.ntiles) return;  // block-uniform
     unsigned key[kRows], val[VALS ? kRows : 1];
     load_tile<VALS>(kin, vin, a, cur, key, val);
-    // The ranking reads and advances s_cnt[wave] with relaxed wavefront-scope atomics (plain ds_read / ds_write that the
-    // compiler neither forwards nor drops): one wave's LDS accesses execute in program order.
-
     while (true) {
         const bool full = (cur + 1u) * kTileElems <= a.n;                          // block-uniform
         const unsigned tile_n = full ? (unsigned)kTileElems : a.n - cur * kTileElems;  // 1 .. 16384
@@ -228,22 +205,7 @@ __global__ __launch_bounds__(kThreads) void sort_pass_kernel(const unsigned* __r
         for (int r = 0; r < kRows; ++r) {
             const bool valid = full || i0 + r * kWave < a.n;
             const unsigned d = (key[r] >> a.shift) & a.mask;
-            // match-any: the valid lanes of this row that hold digit d. Per digit bit one ballot m and, with x = 0 / ~0
-            // for a clear / set bit, peers &= ~(m ^ x), which is m or ~m (one three-input bit operation per half).
-            const unsigned long long vmask = __ballot(valid);
-            unsigned plo = (unsigned)vmask, phi = (unsigned)(vmask >> 32);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const unsigned x = (unsigned)((int)(d << (31 - b)) >> 31);
-                const unsigned long long m = __ballot(x != 0u);
-                plo &= ~((unsigned)m ^ x);
-                phi &= ~((unsigned)(m >> 32) ^ x);
-            }
-            const unsigned below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-            const unsigned total = (unsigned)(__popc(plo) + __popc(phi));
-            const unsigned old = cnt_load(&s_cnt[wave][d]);  // every peer reads the counter before the last peer advances it
-            rank[r] = old + below;
-            if (valid && below + 1u == total) cnt_store(&s_cnt[wave][d], old + total);
+            rank[r] = rank_row(d, valid, s_cnt[wave]);  // match-any on the wave's counters (radix_rank.h)
         }
         __syncthreads();
         // ---- (c) thread d: digit d's count of the tile, the waves' exclusive offsets, and the tile's granule

@@ -135,5 +135,10 @@ __host__ __device__ inline long long pad2(long long t) { return (t + 1) & ~1LL; 
 __host__ __device__ inline long long pad4(long long t) { return (t + 3) & ~3LL; }
 inline size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
 inline bool misaligned(const void* p, unsigned mask = 15u) { return (((uintptr_t)p) & mask) != 0; }
+// [p, p + pb) and [q, q + qb) share a byte; a NULL or empty range shares none
+inline bool ranges_overlap(const void* p, size_t pb, const void* q, size_t qb) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && pb && qb && a < b + qb && b < a + pb;
+}
 
 }  // namespace pcmx
