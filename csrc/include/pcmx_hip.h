@@ -373,6 +373,37 @@ int pcmx_segment_reduce_i32(const int32_t* x, long long n, const int32_t* offset
  * PCMX_ERR_ARG, nothing launched); n == 0 returns 0 and touches nothing. */
 int pcmx_segment_heads(const int32_t* offsets, long long S, long long n, unsigned char* heads, hipStream_t s);
 
+/* ---------------------------------------------------------------- sort inside ragged segments (offsets) */
+/* Every segment [offsets[j], offsets[j+1]) of n 32-bit keys, j < S, sorted on its own: restricted to a segment the
+ * outputs equal pcmx_radix_sort applied to that slice, bit for bit (same transformed keys, stable, F32 keys canonical
+ * on output, values moved as bits), except that PCMX_SORT_INDEX gives FLAT int32 indices into keys_in (the position
+ * within the segment plus offsets[j]). keys_out / vals_out hold n entries, laid out as keys_in. offsets as for
+ * pcmx_segment_reduce_*: S + 1 int32 values in device memory with the PRECONDITION 0 <= offsets[0] <= ... <=
+ * offsets[S] <= n, not checked: every offset is clamped to [0, n] where it is read and a negative length counts as 0,
+ * so offsets that break it give an unspecified result but every load and store stays inside the buffers. Keys before
+ * offsets[0] and from offsets[S] on belong to no segment: they are copied through with their bits unchanged
+ * (PCMX_SORT_INDEX: their own position); the two offsets are read on the device.
+ * A segment of at most PCMX_SEGSORT_MAX_LEN keys is sorted inside one CU by one wave or one 512-thread block
+ * (csrc/kernels/segsort.hip: segments are listed by length class on the device, every class runs a fixed grid over its
+ * list). A LONGER segment is not sorted here: its part of the outputs is NOT WRITTEN, and it is reported in the
+ * summary, 4 uint32 at byte PCMX_SEGSORT_SUMMARY_OFFSET of the workspace, valid once the stream has run the call:
+ * {segments longer than PCMX_SEGSORT_MAX_LEN, the keys in them, the longest length of any segment, 0}.
+ * mode is PCMX_SORT_KEYS / PAIRS / INDEX as for pcmx_radix_sort (keys_out may be NULL in INDEX mode), optionally OR-ed
+ * with PCMX_SEGSORT_GRID(m), 1 <= m <= 64: m blocks per compute unit in every class launch (the lab's knob).
+ * No error word, no block waits for another, no host sync; the inputs are never written. The workspace
+ * (pcmx_segment_sort_workspace_bytes, 256 + 4 S bytes rounded up; one call in flight per workspace) and the key / value
+ * buffers 16-B aligned, offsets 4-B aligned. PCMX_ERR_ARG with nothing launched and nothing written: a NULL or
+ * misaligned pointer, an output that overlaps an input, the offsets or another output, a workspace that overlaps any
+ * of them, a bad key type, mode or bit range, n or S negative or above 2^30 - 1. n == 0 clears the summary and
+ * launches nothing else; S == 0 copies everything through. */
+#define PCMX_SEGSORT_MAX_LEN 16384
+#define PCMX_SEGSORT_SUMMARY_OFFSET 128
+#define PCMX_SEGSORT_GRID(m) ((m) << 8)
+long long pcmx_segment_sort_workspace_bytes(long long n, long long S);
+int pcmx_segment_sort_b32(const void* keys_in, void* keys_out, const void* vals_in, void* vals_out, long long n,
+                          const int32_t* offsets, long long S, int key_type, int mode, int descending, int begin_bit,
+                          int end_bit, void* workspace, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

@@ -1002,6 +1002,48 @@ at::Tensor segment_heads(const at::Tensor& offsets, int64_t n, const at::Tensor&
     return heads;
 }
 
+// ---------------------------------------------------------------- sort inside ragged segments (offsets)
+// (sorted keys [n], values or flat int32 indices [n], the 4-word int32 summary) of the flattened keys with every segment
+// sorted on its own (csrc/kernels/segsort.hip). mode: PCMX_SORT_* | PCMX_SEGSORT_GRID(m). With want_keys false (INDEX
+// mode) the first tensor is empty and no keys are written. Segments longer than PCMX_SEGSORT_MAX_LEN are left UNWRITTEN
+// in the outputs and counted in the summary, a view of the workspace the caller may read (16 bytes) or drop: nothing
+// synchronises here. Contiguous 16-B aligned inputs (copied when they are not), fresh outputs.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> segment_sort(const at::Tensor& keys, const c10::optional<at::Tensor>& values,
+                                                            const at::Tensor& offsets, int64_t mode, bool descending,
+                                                            int64_t begin_bit, int64_t end_bit, bool want_keys) {
+    const int key_type = sort_key_type(keys, "segment_sort");
+    TORCH_CHECK(keys.is_contiguous(), "segment_sort: the keys must be contiguous");
+    const at::DeviceGuard g(keys.device());
+    at::Tensor oc = segment_offsets(offsets, keys, "segment_sort");
+    const int64_t n = keys.numel(), S = oc.numel() - 1, base_mode = mode & 0xff;
+    TORCH_CHECK(n < (1LL << 30) && S < (1LL << 30), "segment_sort: fewer than 2^30 keys and segments");
+    at::Tensor kc = aligned_contig(keys).view(-1), vc;
+    if (values.has_value()) {
+        TORCH_CHECK(values->device() == keys.device(), "segment_sort: values must be on the keys' device");
+        TORCH_CHECK(values->scalar_type() == at::kFloat || values->scalar_type() == at::kInt,
+                    "segment_sort: values have dtype ", values->scalar_type(), ", expected float32 or int32");
+        TORCH_CHECK(values->numel() == n && values->is_contiguous(), "segment_sort: values must be contiguous with one "
+                    "entry per key");
+        vc = aligned_contig(*values).view(-1);
+    }
+    TORCH_CHECK(values.has_value() == (base_mode == PCMX_SORT_PAIRS), "segment_sort: values go with PCMX_SORT_PAIRS and only with it");
+    TORCH_CHECK(want_keys || base_mode == PCMX_SORT_INDEX, "segment_sort: only PCMX_SORT_INDEX can go without sorted keys");
+    at::Tensor ko = at::empty({want_keys ? n : 0}, keys.options()), vo;
+    if (base_mode == PCMX_SORT_PAIRS) vo = at::empty({n}, values->options());
+    else vo = at::empty({base_mode == PCMX_SORT_INDEX ? n : 0}, keys.options().dtype(at::kInt));
+    at::Tensor ws = workspace(keys, pcmx_segment_sort_workspace_bytes(n, S));
+    at::Tensor summary = ws.narrow(0, PCMX_SEGSORT_SUMMARY_OFFSET, 16).view(at::kInt);
+    if (n == 0) {  // empty tensors have no base pointer
+        summary.zero_();
+        return {ko, vo, summary};
+    }
+    check_rc(pcmx_segment_sort_b32(kc.data_ptr(), want_keys ? ko.data_ptr() : nullptr, values.has_value() ? vc.data_ptr() : nullptr,
+                                   base_mode == PCMX_SORT_KEYS ? nullptr : vo.data_ptr(), n, oc.data_ptr<int32_t>(), S, key_type,
+                                   (int)mode, descending ? 1 : 0, (int)begin_bit, (int)end_bit, ws.data_ptr(), cur_stream(keys)),
+             "segment_sort");
+    return {ko, vo, summary};
+}
+
 // ---------------------------------------------------------------- SGEMM
 at::Tensor sgemm_out(const at::Tensor& a, const at::Tensor& b, at::Tensor c, double alpha, double beta, int64_t variant) {
     check_gpu(a, "a", at::kFloat), check_gpu(b, "b", at::kFloat), check_gpu(c, "c", at::kFloat);
@@ -1574,6 +1616,7 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("searchsorted(Tensor sorted_sequence, Tensor values, bool right=False, bool descending=False, bool values_sorted=False, Tensor(a!)? out=None) -> Tensor");
     m.def("segment_reduce(Tensor x, Tensor offsets, int op, Tensor(a!)? out=None) -> Tensor");
     m.def("segment_heads(Tensor offsets, int n, Tensor like) -> Tensor");
+    m.def("segment_sort(Tensor keys, Tensor? values, Tensor offsets, int mode, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor, Tensor)");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
     m.def("sgemm_simt(Tensor a, Tensor b) -> Tensor");
@@ -1639,6 +1682,7 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("searchsorted", searchsorted);
     m.impl("segment_reduce", segment_reduce);
     m.impl("segment_heads", segment_heads);
+    m.impl("segment_sort", segment_sort);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);
     m.impl("sgemm_simt", sgemm_simt);

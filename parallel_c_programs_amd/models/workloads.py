@@ -1551,10 +1551,81 @@ class Ragged(Workload):
         return rep
 
 
+class SegSort(Ragged):
+    """Sort inside ragged segments given by offsets (csrc/kernels/segsort.hip) on n keys per GPU: mode "keys"
+    (ops.segment_sort_keys), "index" (ops.segment_sort) or "pairs" (ops.segment_sort_by_key with the keys as their own
+    payload). dist places the segment borders as in the ragged workload ("uniform", "equal", "powerlaw", "empty"); dtype
+    f32 (multiples of 1/64 from a normal distribution, so every longer segment has ties) or i32 (the full range). route
+    and max_len are the ops'. No communication (weak scaling)."""
+
+    MODES = ("keys", "index", "pairs")
+
+    def __init__(self, ctx, n=1 << 28, mean_len=100.0, dist="uniform", mode="keys", dtype="f32", descending=False,
+                 route=None, max_len=None, **_):
+        if mode not in self.MODES:
+            raise ValueError(f"segsort mode {mode!r}: one of {self.MODES}")
+        Ragged.__init__(self, ctx, n, mean_len, dist, "min", dtype)  # the offsets; x is replaced below
+        self.name = "segsort"
+        self.cfg = {"n": int(n), "mean_len": float(mean_len), "dist": dist, "mode": mode, "dtype": dtype,
+                    "descending": bool(descending), "route": route, "max_len": max_len}
+        self.mode, self.descending, self.route = mode, bool(descending), route
+        self.max_len = None if max_len is None else int(max_len)
+        g = torch.Generator(device=ctx.device).manual_seed(20000 + ctx.rank)
+        if dtype == "f32":
+            self.x = torch.round(torch.randn(int(n), device=ctx.device, generator=g) * 64) / 64
+        else:
+            self.x = torch.randint(-(1 << 31), 1 << 31, (int(n),), device=ctx.device, generator=g,
+                                   dtype=torch.int64).to(torch.int32)
+        self.seg_ids = None  # torch_step's segment ids, made on first use
+
+    def _run(self, x, offsets):
+        kw = dict(descending=self.descending, route=self.route, max_len=self.max_len)
+        if self.mode == "keys":
+            return (ops.segment_sort_keys(x, offsets, **kw),)
+        if self.mode == "index":
+            return ops.segment_sort(x, offsets, **kw)
+        return ops.segment_sort_by_key(x, x, offsets, **kw)
+
+    def step(self):
+        self.out = self._run(self.x, self.offsets)
+
+    def torch_step(self):
+        """What a torch caller composes (the vendor bar): a stable sort of the keys, then a stable sort of the segment
+        ids (keys behind the last offset form one more group: the same work)."""
+        if self.seg_ids is None:
+            self.seg_ids = torch.searchsorted(self.offsets.long(), torch.arange(self.x.numel(), device=self.x.device),
+                                              right=True)
+        v, i = torch.sort(self.x, stable=True, descending=self.descending)
+        order = i[torch.sort(self.seg_ids[i], stable=True).indices]
+        return self.x[order], order
+
+    def work_per_step(self):
+        # the bytes a caller sees move: the keys and the offsets read once, and what is written
+        n = self.x.numel()
+        return float({"keys": 8 * n, "index": 12 * n, "pairs": 16 * n}[self.mode] + 4 * (self.segments() + 1))
+
+    def check(self, reduce: bool = True):
+        """Every output of the timed step against the host path of the same op on a host copy, bit for bit. Local only."""
+        ref = self._run(self.x.cpu(), self.offsets.cpu())
+        out = [t.cpu() for t in self.out]
+        ok = len(out) == len(ref) and all(a.dtype == b.dtype and a.shape == b.shape and
+                                          torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(out, ref))
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"elements_checked": self.x.numel(), "exact_vs_host": True, "check_passed": ok}
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = Workload.report(self, seconds, steps)
+        rep["gkeys_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        rep["segments"] = self.segments()
+        return rep
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
              "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
-             "merge": Merge, "rowsort": RowSort, "axis": Axis, "ragged": Ragged}
+             "merge": Merge, "rowsort": RowSort, "axis": Axis, "ragged": Ragged, "segsort": SegSort}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

@@ -13,6 +13,9 @@ from .vector import (CMP_CODES, OP_CODES, argsort, axpy_, bincount, bucketize, c
                      gather_, histc, histogram, kth_value, merge, merge_by_key, merge_keys, rand_uniform_, reduce, reduce_by_key, run_length_encode, run_positions, scan,
                      scan_by_key, scan_check, searchsorted, segment_reduce, segment_scan, segmented_scan, select, select_indices, sort, sort_by_key, sort_keys, sum_by_key,
                      topk, unique, unique_consecutive, vadd, vmul)
+# segment_sort_keys / segment_sort / segment_argsort / segment_sort_by_key sort inside the same ragged segments
+# (csrc/kernels/segsort.hip; SEGSORT_CLASS_LIMITS, SEGSORT_MAX_LEN, SEGSORT_GRID_MULT)
+from .vector import segment_argsort, segment_sort, segment_sort_by_key, segment_sort_keys
 
 __all__ = [
     "sgemm", "sgemm_out", "sgemm_simt", "sgemm_naive_host",
@@ -29,4 +32,5 @@ __all__ = [
     "bincount", "histc", "histogram",
     "merge_keys", "merge", "merge_by_key", "searchsorted", "bucketize",
     "segment_reduce", "segment_scan",
+    "segment_sort_keys", "segment_sort", "segment_argsort", "segment_sort_by_key",
 ]

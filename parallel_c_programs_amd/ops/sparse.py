@@ -427,6 +427,23 @@ def spmv(m: CSR, x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def sort_csr_columns(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, max_len: int | None = None):
+    """(col, val) with the entries of every CSR row ordered by column, entries of equal column in their input order:
+    ops.segment_sort_by_key over the rows (csrc/kernels/segsort.hip on the GPU). row_ptr is int32 or int64 [rows + 1]
+    (a CSR's int64 row_ptr is narrowed; nnz < 2^30), col int32 [nnz], val float32 or int32 [nnz], all on one device.
+    Entries outside [row_ptr[0], row_ptr[-1]) stay where they are. max_len: a promised bound on the row length (no host
+    sync when it is at most SEGSORT_MAX_LEN). The inputs are not modified."""
+    from .vector import segment_sort_by_key
+
+    if row_ptr.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"row_ptr must be int32 or int64, got {row_ptr.dtype}")
+    if col.dtype != torch.int32:
+        raise TypeError(f"col must be int32, got {col.dtype}")
+    if col.dim() != 1 or val.shape != col.shape:
+        raise ValueError(f"col and val must be 1-D with one entry per nonzero, got {tuple(col.shape)} and {tuple(val.shape)}")
+    return segment_sort_by_key(col.contiguous(), val.contiguous(), row_ptr.to(torch.int32).contiguous(), max_len=max_len)
+
+
 def spmv_banded(vals: torch.Tensor, row_off: torch.Tensor, n: int, a: int, b: int, c: int, d: int, e: int,
                 x: torch.Tensor, variant: int = 8) -> torch.Tensor:
     """Banded product with implicit columns (the reference's s_matrix `multiply`, spmv.c:212-329). GPU variant 8

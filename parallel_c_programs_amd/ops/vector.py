@@ -1599,3 +1599,226 @@ def segment_scan(x: torch.Tensor, offsets: torch.Tensor, op: str = "sum", exclus
         o = offsets.long()
         heads[o[(o >= 0) & (o < n)]] = 1
     return segmented_scan(x, heads, op, exclusive, out)
+
+
+# ---------------------------------------------------------------- sort inside ragged segments (offsets)
+# The sorting member of the offsets family: every segment x.flatten()[offsets[j] : offsets[j+1]] sorted on its own, the
+# column indices of each CSR row, the candidates of each query, the tokens of each sequence of a packed batch. Restricted
+# to a segment every output equals the 1-D op (sort_keys / sort / argsort / sort_by_key with the same descending and
+# bits) on that slice, BIT FOR BIT: stable, ties by lowest position, float32 keys canonical, values moved as bits.
+#  * offsets as for segment_reduce: int32, 1-D, contiguous, on x's device, S + 1 >= 1 entries, PRECONDITION
+#    0 <= offsets[0] <= ... <= offsets[S] <= n, checked only with validate=True (one host sync, ValueError naming the
+#    first bad entry). Offsets that break it give an unspecified result; every offset is clamped to [0, n] and a
+#    negative length counts as 0, so nothing outside the tensors is read or written. n and S are at most 2^30 - 1.
+#  * indices are FLAT int32 indices into x.flatten(): values.flatten() == x.flatten()[indices.flatten()] as bits for
+#    int32 keys (float32 values are canonical), and indices[b:e] - b is the 1-D argsort of the slice.
+#  * Elements before offsets[0] and from offsets[S] on belong to no segment: they come through with their bits unchanged
+#    (NOT canonical) and their index is their own position; the two offsets are read on the device.
+#  * On the GPU (csrc/kernels/segsort.hip; no counterpart in the reference programs) the segments are listed by length
+#    class on the device and every class runs the row sort's in-CU passes over its list: one wave per segment up to
+#    SEGSORT_CLASS_LIMITS[3] keys, one 512-thread block up to SEGSORT_MAX_LEN. A class launch is a FIXED grid of
+#    SEGSORT_GRID_MULT blocks per compute unit striding over the list, so the launch needs no count on the host.
+#    Segments LONGER than SEGSORT_MAX_LEN take the device-wide kernels: their keys are gathered into a packed buffer,
+#    sorted by one stable index sort, then by long-segment rank (bits = ceil(log2 count); skipped for a single long
+#    segment) and scattered back.
+#  * HOST SYNCS: the host learns whether the long route is needed from a 16-byte summary: ONE host sync per call, and
+#    none after it when no segment is that long (the long route itself synchronises again to size its buffers).
+#    max_len=M is the caller's promise that no segment is longer than M: with M <= SEGSORT_MAX_LEN the call does not
+#    synchronise at all. A segment that breaks the promise gets an unspecified result inside its own range (with M <=
+#    SEGSORT_MAX_LEN: one longer than SEGSORT_MAX_LEN is left unwritten). validate=True also checks max_len.
+#  * route: None is the rule above; "classes" never takes the long route and raises ValueError when the summary shows
+#    a segment above SEGSORT_MAX_LEN (with max_len <= SEGSORT_MAX_LEN nothing is read back, so nothing is raised);
+#    "global" sorts ALL keys with the device-wide kernels: a stable index sort, then a stable sort by segment id with
+#    bits = ceil(log2(S + 2)), any lengths at about twice a flat sort: the route callers had before, the A/B partner and
+#    the tests' cross-check. route is validated on CPU tensors too; "classes" refuses long segments there as well.
+#  * CPU tensors: two stable torch.sort on the host (by key, then by segment id).
+#  * The class borders are the row sort's instantiations under its measured border ROWSORT_WAVE_COLS (wave against block
+#    at equal rows, above); they and SEGSORT_GRID_MULT are NOT MEASURED for ragged lengths
+#    (profiles/r20_segsort/README.md holds the footprint of every instantiation and the lab's method).
+#  * Measured on one MI355X (scripts/segsort_lab.py, profiles/r20_segsort/README.md): 2^28 keys NOT MEASURED yet. The
+#    lab's launch-bound dry run at 2^21 float32 keys, ours / route="global" / the same composition in torch, ms with
+#    indices: equal segments of 32 0.18 / 0.84 / 0.51, of 100 0.15 / 0.73 / 0.51, of 4096 0.16 / 0.70 / 0.50, of 16384
+#    0.17 / 0.57 / 0.51, uniform borders of mean 100 0.16 / 0.70 / 0.50 (3.3x-4.8x global, 2.8x-3.4x torch). SLOWER at
+#    that size: segments of 4 keys, keys alone 0.72 / 0.65 / 0.50 (one wave per 4 keys); power-law rows of mean 100
+#    0.62-0.69 against torch 0.50-0.51 and one segment 1.41-1.48 against 0.46-0.59 (both take the long route); and
+#    against ops.sort(dim=-1) on the same equal-length data the front end costs 1.5x-3.7x (eleven more launches and the
+#    read-back on a 0.04-0.08 ms sort).
+SEGSORT_MAX_LEN = ROWSORT_MAX_COLS    # csrc/include/pcmx_hip.h PCMX_SEGSORT_MAX_LEN: one block's LDS
+SEGSORT_CLASS_LIMITS = (64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384)  # segsort.hip: the capacity of every class
+SEGSORT_WAVE_CLASSES = 4              # the first four classes put 4 segments into a block (one wave each), the rest one
+SEGSORT_GRID_MULT = 8                 # segsort.hip kGridMult: blocks per compute unit of a class launch; not measured
+SEGSORT_MAX_S = (1 << 30) - 1
+_SEGSORT_ROUTES = (None, "classes", "global")
+
+
+def _segment_ids(offsets: torch.Tensor, n: int) -> torch.Tensor:
+    """int64 [n]: 0 before offsets[0], j + 1 inside segment j, S + 1 from offsets[S] on (offsets clamped to [0, n])."""
+    o = offsets.long().clamp(0, n)
+    return torch.searchsorted(o, torch.arange(n, device=offsets.device), right=True)
+
+
+def _check_segsort(keys, values, offsets, mode, bits, validate, max_len, route, name: str):
+    """(compared bits, S) after every argument check of the four ops."""
+    nbits = _check_sort_keys(keys, bits, "keys" if mode == "pairs" else "x")
+    if offsets.numel() - 1 > SEGSORT_MAX_S:
+        raise ValueError(f"{name}: {offsets.numel() - 1} segments; at most 2^30 - 1")
+    s = _check_segments(keys, offsets, "sum", name)
+    if mode == "pairs":
+        if values.dtype not in (torch.float32, torch.int32):
+            raise TypeError(f"{name}: values must be float32 or int32, got {values.dtype}")
+        if values.shape != keys.shape:
+            raise ValueError(f"{name}: values must have the keys' shape {tuple(keys.shape)}, got {tuple(values.shape)}")
+        if values.device != keys.device:
+            raise ValueError(f"{name}: values are on {values.device}, the keys on {keys.device}")
+        if not values.is_contiguous():
+            raise ValueError(f"{name}: values must be contiguous")
+    if route not in _SEGSORT_ROUTES:
+        raise ValueError(f"{name}: route must be one of {_SEGSORT_ROUTES}, got {route!r}")
+    if max_len is not None:
+        if isinstance(max_len, bool) or not isinstance(max_len, int):
+            raise TypeError(f"{name}: max_len must be an int or None, got {type(max_len).__name__}")
+        if max_len < 0:
+            raise ValueError(f"{name}: max_len must not be negative, got {max_len}")
+    if validate:
+        _validate_offsets(offsets, keys.numel())
+        if max_len is not None and s > 0:
+            lens = offsets[1:].long() - offsets[:-1].long()
+            j = int(torch.argmax(lens))
+            if int(lens[j]) > max_len:
+                raise ValueError(f"{name}: segment {j} has {int(lens[j])} keys, more than max_len = {max_len}")
+    return nbits, s
+
+
+def _segsort_by_ids(pk: torch.Tensor, sid: torch.Tensor, groups: int, descending: bool, nbits: int, want_keys: bool,
+                    want_perm: bool):
+    """(sorted keys or None, int32 permutation or None) of the packed keys pk sorted inside the groups that the
+    non-decreasing int32 ids sid (< groups) give, with the device-wide kernels: one stable index sort of all keys, then
+    a stable pair sort by group id per wanted stream (skipped for one group)."""
+    ks, perm = ops().sort_index(pk, descending, 0, nbits, True)
+    if groups > 1:
+        gid = sid[perm.long()]
+        gbits = (groups - 1).bit_length()
+        if want_keys:
+            ks = ops().sort_pairs(gid, ks, False, 0, gbits)[1]
+        if want_perm:
+            perm = ops().sort_pairs(gid, perm, False, 0, gbits)[1]
+    return (ks if want_keys else None), (perm if want_perm else None)
+
+
+def _segsort_long(xf, vf, offsets, ko, po, mode: str, descending: bool, nbits: int, n_long: int, long_keys: int) -> None:
+    """Sorts the n_long segments above SEGSORT_MAX_LEN (long_keys keys together, both from the kernel's summary) into
+    the outputs ko / po, which the class kernels left unwritten there."""
+    n, dev = xf.numel(), xf.device
+    o = offsets.long().clamp(0, n)
+    lens = (o[1:] - o[:-1]).clamp(min=0)
+    ids = torch.nonzero(lens > SEGSORT_MAX_LEN).view(-1)[:n_long]
+    ll, starts = lens[ids], o[:-1][ids]
+    rank = torch.repeat_interleave(torch.arange(ids.numel(), device=dev), ll, output_size=long_keys)
+    src = starts[rank] + (torch.arange(long_keys, device=dev) - (torch.cumsum(ll, 0) - ll)[rank])  # < n
+    pk = xf.view(torch.int32)[src].view(xf.dtype)
+    ks, perm = _segsort_by_ids(pk, rank.int(), n_long, descending, nbits, ko is not None, po is not None)
+    if ko is not None:
+        ko.view(torch.int32)[src] = ks.view(torch.int32)
+    if po is not None:
+        flat = src[perm.long()]
+        po.view(torch.int32)[src] = vf.view(torch.int32)[flat] if mode == "pairs" else flat.int()
+
+
+def _segsort_gpu(xf, vf, offsets, mode: str, descending: bool, nbits: int, max_len, route, grid_mult: int = 0):
+    """(keys or None, payload or None), flat, of the segment sort of xf on the GPU."""
+    n, s = xf.numel(), offsets.numel() - 1
+    want_keys, want_payload = mode != "argsort", mode != "keys"
+    if route == "global":
+        sid = _segment_ids(offsets, n)
+        inside = (sid >= 1) & (sid <= s)
+        ks, perm = _segsort_by_ids(xf, sid.int(), s + 2, descending, nbits, want_keys, want_payload)
+        ko = po = None
+        if want_keys:  # the groups 0 and S + 1 lie where they were: put their elements back as they came
+            ko = torch.where(inside, ks.view(torch.int32), xf.view(torch.int32)).view(xf.dtype)
+        if want_payload:
+            perm = torch.where(inside, perm, torch.arange(n, device=xf.device, dtype=torch.int32))
+            po = vf.view(torch.int32)[perm.long()].view(vf.dtype) if mode == "pairs" else perm
+        return ko, po
+    code = {"keys": _MODE_KEYS, "pairs": _MODE_PAIRS}.get(mode, _MODE_INDEX) | (int(grid_mult) << 8)
+    ko, po, summary = ops().segment_sort(xf, vf, offsets, code, descending, 0, nbits, want_keys)
+    ko, po = (ko if want_keys else None), (po if want_payload else None)
+    if max_len is not None and max_len <= SEGSORT_MAX_LEN:
+        return ko, po
+    n_long, long_keys, longest, _ = summary.tolist()  # the one host sync: 16 bytes
+    if n_long:
+        if route == "classes":
+            raise ValueError(f"segment sort: route 'classes' takes segments of at most {SEGSORT_MAX_LEN} keys; {n_long} "
+                             f"are longer, the longest has {longest}")
+        _segsort_long(xf, vf, offsets, ko, po, mode, descending, nbits, n_long, long_keys)
+    return ko, po
+
+
+def _segsort_host(xf, vf, offsets, mode: str, descending: bool, nbits: int, route):
+    n, s = xf.numel(), offsets.numel() - 1
+    if route == "classes" and s > 0:
+        o = offsets.long().clamp(0, n)
+        longest = int((o[1:] - o[:-1]).max())
+        if longest > SEGSORT_MAX_LEN:
+            raise ValueError(f"segment sort: route 'classes' takes segments of at most {SEGSORT_MAX_LEN} keys; the longest "
+                             f"has {longest}")
+    sid = _segment_ids(offsets, n)
+    inside = (sid >= 1) & (sid <= s)
+    order = _host_order(xf, descending, nbits)
+    order = order[torch.sort(sid[order], stable=True).indices]
+    order = torch.where(inside, order, torch.arange(n))
+    xb = xf.view(torch.int32)
+    ko = None if mode == "argsort" else torch.where(inside, _canonical_f32(xb[order].view(xf.dtype)).view(torch.int32),
+                                                    xb).view(xf.dtype)
+    po = None if mode == "keys" else (vf.view(torch.int32)[order].view(vf.dtype) if mode == "pairs" else order.int())
+    return ko, po
+
+
+def _segment_sort(keys, values, offsets, mode, descending, bits, validate, max_len, route, name, grid_mult=0):
+    nbits, _ = _check_segsort(keys, values, offsets, mode, bits, validate, max_len, route, name)
+    xf = keys.view(-1)
+    vf = values.view(-1) if mode == "pairs" else None
+    if xf.numel() == 0:
+        ko = None if mode == "argsort" else xf.clone()
+        po = None if mode == "keys" else (vf.clone() if mode == "pairs" else xf.new_empty(0, dtype=torch.int32))
+    elif keys.is_cuda:
+        ko, po = _segsort_gpu(xf, vf, offsets, mode, bool(descending), nbits, max_len, route, grid_mult)
+    else:
+        ko, po = _segsort_host(xf, vf, offsets, mode, bool(descending), nbits, route)
+    return (None if ko is None else ko.view(keys.shape)), (None if po is None else po.view(keys.shape))
+
+
+def segment_sort_keys(x: torch.Tensor, offsets: torch.Tensor, descending: bool = False, bits: int | None = None,
+                      validate: bool = False, max_len: int | None = None, route: str | None = None) -> torch.Tensor:
+    """x (float32 or int32, contiguous, read flattened) with every segment x.flatten()[offsets[j] : offsets[j+1]] sorted
+    on its own, in x's shape: each segment equals sort_keys of that slice bit for bit (rules above). Elements outside
+    [offsets[0], offsets[S]) come through unchanged. x is never modified. One host sync of 16 bytes (is any segment
+    above SEGSORT_MAX_LEN?) unless max_len <= SEGSORT_MAX_LEN promises there is none: then the call does not
+    synchronise, and a segment that breaks the promise gets an unspecified result inside its own range."""
+    return _segment_sort(x, None, offsets, "keys", descending, bits, validate, max_len, route, "segment_sort_keys")[0]
+
+
+def segment_sort(x: torch.Tensor, offsets: torch.Tensor, descending: bool = False, bits: int | None = None,
+                 validate: bool = False, max_len: int | None = None, route: str | None = None):
+    """(values, indices) in x's shape: segment_sort_keys(x, offsets) and the FLAT int32 index into x.flatten() of every
+    output element, so indices[b:e] - b is the stable argsort of the slice; outside [offsets[0], offsets[S]) the index
+    is the element's own position. Host syncs and max_len as for segment_sort_keys (one sync of 16 bytes; none with
+    max_len <= SEGSORT_MAX_LEN, a broken promise giving an unspecified result in bounds)."""
+    return _segment_sort(x, None, offsets, "index", descending, bits, validate, max_len, route, "segment_sort")
+
+
+def segment_argsort(x: torch.Tensor, offsets: torch.Tensor, descending: bool = False, bits: int | None = None,
+                    validate: bool = False, max_len: int | None = None, route: str | None = None) -> torch.Tensor:
+    """The indices of segment_sort alone; no sorted-keys tensor is written. Host syncs and max_len as for
+    segment_sort_keys (one sync of 16 bytes; none with max_len <= SEGSORT_MAX_LEN, a broken promise giving an
+    unspecified result in bounds)."""
+    return _segment_sort(x, None, offsets, "argsort", descending, bits, validate, max_len, route, "segment_argsort")[1]
+
+
+def segment_sort_by_key(keys: torch.Tensor, values: torch.Tensor, offsets: torch.Tensor, descending: bool = False,
+                        bits: int | None = None, validate: bool = False, max_len: int | None = None,
+                        route: str | None = None):
+    """(keys_sorted, values_sorted) in the keys' shape: values (float32 or int32, the keys' shape and device, contiguous,
+    moved as bits) reordered with their keys inside every segment; sort_by_key of every slice, bit for bit. Host syncs
+    and max_len as for segment_sort_keys (one sync of 16 bytes; none with max_len <= SEGSORT_MAX_LEN, a broken promise
+    giving an unspecified result in bounds)."""
+    return _segment_sort(keys, values, offsets, "pairs", descending, bits, validate, max_len, route, "segment_sort_by_key")
