@@ -570,6 +570,14 @@ int pcmx_spmv_banded(const float* vals, const long long* row_off, int n, int a, 
  * allocation). 1 and 8 fall back to 0 for rows above 16 x 64 nonzeros. Any other variant: PCMX_ERR_ARG. */
 int pcmx_spmv_banded_variant(const float* vals, const long long* row_off, int n, int a, int b, int c, int d, int e,
                              const float* x, float* y, int variant, hipStream_t s);
+/* Which kernel pcmx_spmv_banded_variant takes for this geometry and variant, from the same host predicate the launcher
+ * dispatches on; launches nothing and reads no device memory. vals_aligned: whether the value array is 16-B aligned.
+ * Returns 0 (one wave per row), 1 (the LDS-window kernel) or 8 (the block stream), or PCMX_ERR_ARG for the geometries
+ * and variants the launcher refuses. *nl (may be NULL): the LDS kernel's instantiation (2, 4, 6, 8, 10, 12 or 16
+ * chunks of 64 nonzeros per row) for 1, and for 8 the one a fall-back would take; 0 otherwise. Geometry only: a stream
+ * capture before the geometry's table exists, or a failed table allocation, still turns 8 into 1 at launch, and a call
+ * with n <= 0 launches nothing. */
+int pcmx_spmv_banded_path(int n, int a, int b, int c, int d, int e, int variant, int vals_aligned, int* nl);
 
 /* ---------------------------------------------------------------- halo pack/unpack */
 int pcmx_pack_edges(const void* tile, int elem_bytes, int H, int W, int ld, void* buf, hipStream_t s);

@@ -1178,29 +1178,58 @@ const pcmx::i32x4* banded_lut_table(const BandGeo& g, hipStream_t s) {
     ent.first = d;
     return reinterpret_cast<const pcmx::i32x4*>(d);
 }
-// Variant 8 launch (block stream over the unclipped rows, the clipped row blocks folded into the same grid);
-// kStreamNotApplicable when the band geometry or the value alignment rules it out.
-int launch_banded_stream(const float* vals, const long long* row_off, int n, int a, int b, int c, int d, int e,
-                         const float* x, float* y, hipStream_t s) {
-    // rows [rlo, rhi) are unclipped (every band inside [0, n)) and all hold L nonzeros
+// Which banded kernel a call takes, decided from the geometry alone: the ONE place the dispatch conditions live (the
+// launcher below and the pcmx_spmv_banded_path query both read it). path 0: one wave per row; 1: the LDS-window kernel
+// spmv_banded_lds_kernel<nl>; 8: the block stream, which the launcher may still turn into 1 (a stream capture or a failed
+// table allocation, banded_lut_table); PCMX_ERR_ARG: refused. The other fields are what the launches need.
+struct BandedPlan {
+    int path, nl;             // nl: the LDS kernel's instantiation (also the fallback of path 8; 0 for path 0)
+    int L, W;                 // nonzeros of an unclipped row, variant 8's window floats per block
+    int rb_lo, rb_hi, nrb;    // row blocks [rb_lo, rb_hi) hold unclipped rows only; nrb row blocks in all
+    size_t lds, lds8;         // dynamic LDS of the row body (variant 1, variant 8's clipped blocks) / of a stream block
+};
+BandedPlan banded_plan(int n, int a, int b, int c, int d, int e, int variant, bool vals_aligned) {
     constexpr int RS = kBandedRows, NV = kStreamNV, XW = kStreamXW;
+    BandedPlan p{};
+    p.path = PCMX_ERR_ARG;
+    // 0: one wave per row; 1: LDS-staged x windows, 16 rows per block, 2 rows per wave in flight; 8: block stream
+    // (16-B loads over each 16-row block's contiguous value range, spmv_banded_stream_kernel), the production path
+    if (a < 1 || b < 0 || c < 0 || d < 0 || e < 0 || (variant != 0 && variant != 1 && variant != 8)) return p;
+    const long long maxrow = 2LL * (a / 2) + 1 + 2LL * c + 2LL * e;  // nonzeros of an unclipped row
+    const long long nl = (maxrow + 63) / 64;
+    p.lds = (size_t)(maxrow + 5 * (RS - 1)) * sizeof(float);
+    if (variant == 0 || nl > 16 || p.lds > 64 * 1024) {  // rows longer than 16 x 64 nonzeros: the wave-per-row kernel
+        p.path = 0;
+        return p;
+    }
+    p.path = 1;
+    p.nl = nl <= 2 ? 2 : nl <= 4 ? 4 : nl <= 6 ? 6 : nl <= 8 ? 8 : nl <= 10 ? 10 : nl <= 12 ? 12 : 16;
+    if (variant != 8) return p;
+    // rows [rlo, rhi) are unclipped (every band inside [0, n)) and all hold L nonzeros
     const int ah = a / 2, r9 = ah + b + c + d + e;
-    const int L = 2 * ah + 1 + 2 * c + 2 * e;
-    const long long maxrow = L;
+    const int L = (int)maxrow;
     const int rlo = r9, rhi = n - r9;
-    const int rb_lo = (rlo + RS - 1) / RS, rb_hi = rhi >= 0 ? rhi / RS : 0, nrb = (n + RS - 1) / RS;
+    p.L = L, p.W = L + 5 * (RS - 1);
+    p.rb_lo = (rlo + RS - 1) / RS, p.rb_hi = rhi >= 0 ? rhi / RS : 0, p.nrb = (n + RS - 1) / RS;
     const long long q = ((long long)L * RS + 6) / 16;  // float4s per wave quarter (lead <= 3)
-    const int W = L + 5 * (RS - 1);
-    const size_t lds_rows = (size_t)(maxrow + 5 * (RS - 1)) * sizeof(float);  // the clipped blocks' row body
-    const size_t lds8 = (size_t)(4 * 256 * XW + ((RS + 3) & ~3) + 16 * ((L + 6) / 4)) * sizeof(float);
+    p.lds8 = (size_t)(4 * 256 * XW + ((RS + 3) & ~3) + 16 * ((L + 6) / 4)) * sizeof(float);
     // the wave-iteration rule needs rows of >= 256 nonzeros, the float4 stream a 16-B aligned vals; the register
     // sets hold NV float4s per lane and XW window floats per thread; the clipped body NL = 16 chunks of 64
+    // (short rows or unaligned values: variant 1 runs instead)
     const bool ok = L >= 256 && L <= 16 * 64 && 4 * ((L + 6) / 4) <= 256 * kLutPer && q <= 64 * NV &&
-                    W + 3 <= XW * 256 && rb_hi > rb_lo &&
-                    !((uintptr_t)vals & 15) && lds_rows <= 64 * 1024 && lds8 <= 64 * 1024;
-    if (!ok) return kStreamNotApplicable;
+                    p.W + 3 <= XW * 256 && p.rb_hi > p.rb_lo && vals_aligned && p.lds8 <= 64 * 1024;
+    if (ok) p.path = 8;
+    return p;
+}
+
+// Variant 8 launch (block stream over the unclipped rows, the clipped row blocks folded into the same grid) of a plan
+// whose path is 8; kStreamNotApplicable when the slot table cannot be had (the caller launches variant 1 instead).
+int launch_banded_stream(const BandedPlan& p, const float* vals, const long long* row_off, int n, int a, int b, int c,
+                         int d, int e, const float* x, float* y, hipStream_t s) {
+    constexpr int RS = kBandedRows;
+    const int rlo = a / 2 + b + c + d + e, rb_lo = p.rb_lo, rb_hi = p.rb_hi;
     BandGeo g{};
-    g.L = L, g.W = W, g.n = n;
+    g.L = p.L, g.W = p.W, g.n = n;
     {
         int lo[5], hi[5], wb = 0, cs = 0;
         band_limits_host(n, a, b, c, d, e, rlo, lo, hi);
@@ -1215,7 +1244,7 @@ int launch_banded_stream(const float* vals, const long long* row_off, int n, int
     // variant 1 runs instead)
     const pcmx::i32x4* lut_g = banded_lut_table(g, s);
     if (!lut_g) return kStreamNotApplicable;
-    const int nfront = rb_lo, back0 = rb_hi, nback = nrb - rb_hi;
+    const int nfront = rb_lo, back0 = rb_hi, nback = p.nrb - rb_hi;
     // first value of row rb_lo * RS: the nonzeros of the clipped rows before it (host sum of row lengths)
     long long off0 = 0;
     for (int r = 0; r < rb_lo * RS; ++r) {
@@ -1223,40 +1252,44 @@ int launch_banded_stream(const float* vals, const long long* row_off, int n, int
         band_limits_host(n, a, b, c, d, e, r, lo, hi);
         for (int k = 0; k < 5; ++k) off0 += hi[k] - lo[k];
     }
-    spmv_banded_stream_kernel<<<nfront + nback + rb_hi - rb_lo, 256, std::max(lds_rows, lds8), s>>>(
+    spmv_banded_stream_kernel<<<nfront + nback + rb_hi - rb_lo, 256, std::max(p.lds, p.lds8), s>>>(
         vals, row_off, n, a, b, c, d, e, nfront, back0, nfront + nback, off0, g, lut_g, rb_lo, x, y);
     return (int)hipGetLastError();
 }
 }  // namespace
 
+extern "C" int pcmx_spmv_banded_path(int n, int a, int b, int c, int d, int e, int variant, int vals_aligned, int* nl) {
+    const BandedPlan p = banded_plan(n, a, b, c, d, e, variant, vals_aligned != 0);
+    if (nl) *nl = p.nl;
+    return p.path;
+}
+
 extern "C" int pcmx_spmv_banded_variant(const float* vals, const long long* row_off, int n, int a, int b, int c, int d,
                                         int e, const float* x, float* y, int variant, hipStream_t s) {
     if (n <= 0) return 0;
-    if (a < 1 || b < 0 || c < 0 || d < 0 || e < 0) return PCMX_ERR_ARG;
-    const long long maxrow = 2LL * (a / 2) + 1 + 2LL * c + 2LL * e;  // nonzeros of an unclipped row
-    const int nl = (int)((maxrow + 63) / 64);
-    // 0: one wave per row; 1: LDS-staged x windows, 16 rows per block, 2 rows per wave in flight; 8: block stream
-    // (16-B loads over each 16-row block's contiguous value range, spmv_banded_stream_kernel), the production path
-    if (variant != 0 && variant != 1 && variant != 8) return PCMX_ERR_ARG;
-    const size_t lds = (size_t)(maxrow + 5 * (kBandedRows - 1)) * sizeof(float);
-    if (variant == 0 || nl > 16 || lds > 64 * 1024) {
+    const BandedPlan p = banded_plan(n, a, b, c, d, e, variant, !((uintptr_t)vals & 15));
+    if (p.path < 0) return p.path;
+    if (p.path == 0) {
         spmv_banded_kernel<<<(n + 3) / 4, 256, 0, s>>>(vals, row_off, n, a, b, c, d, e, x, y);
         return (int)hipGetLastError();
     }
-    if (variant == 8) {
-        // (short rows, unaligned values, a stream capture or a failed table allocation: variant 1 runs instead)
-        const int rc = launch_banded_stream(vals, row_off, n, a, b, c, d, e, x, y, s);
+    if (p.path == 8) {
+        // (a stream capture or a failed table allocation: variant 1 runs instead)
+        const int rc = launch_banded_stream(p, vals, row_off, n, a, b, c, d, e, x, y, s);
         if (rc != kStreamNotApplicable) return rc;
     }
     const int grid = (n + kBandedRows - 1) / kBandedRows;
-#define PCMX_BANDED(NL) spmv_banded_lds_kernel<NL><<<grid, 256, lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y)
-    if (nl <= 2) PCMX_BANDED(2);
-    else if (nl <= 4) PCMX_BANDED(4);
-    else if (nl <= 6) PCMX_BANDED(6);
-    else if (nl <= 8) PCMX_BANDED(8);
-    else if (nl <= 10) PCMX_BANDED(10);
-    else if (nl <= 12) PCMX_BANDED(12);
-    else PCMX_BANDED(16);
+#define PCMX_BANDED(NL) \
+    case NL: spmv_banded_lds_kernel<NL><<<grid, 256, p.lds, s>>>(vals, row_off, n, a, b, c, d, e, x, y); break
+    switch (p.nl) {
+        PCMX_BANDED(2);
+        PCMX_BANDED(4);
+        PCMX_BANDED(6);
+        PCMX_BANDED(8);
+        PCMX_BANDED(10);
+        PCMX_BANDED(12);
+        default: PCMX_BANDED(16);
+    }
 #undef PCMX_BANDED
     return (int)hipGetLastError();
 }
