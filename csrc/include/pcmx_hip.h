@@ -63,6 +63,17 @@ int pcmx_reduce_f32(const float* x, long long n, int op, float* out, void* works
 int pcmx_reduce_i32(const int32_t* x, long long n, int op, int32_t* out, void* workspace, hipStream_t s);
 /* out[0] = sum a*b */
 int pcmx_dot_f32(const float* a, const float* b, long long n, float* out, void* workspace, hipStream_t s);
+/* The same launches with the first pass's grid capped at max_blocks instead of 16384 (csrc/kernels/reduce.hip): the
+ * blocks then grid-stride, so a cap of 3 or 7 takes the second and third trip of that loop at a few hundred thousand
+ * elements (the production grid needs more than 2^26). The entries above are these with 16384. max_blocks outside
+ * 1..16384, n < 0, an unknown op, a NULL or misaligned workspace or a misaligned x / a / b: PCMX_ERR_ARG, nothing
+ * launched, out not written. The workspace is pcmx_reduce_workspace_bytes(n) whatever the cap.
+ * A float sum starts from +0.0 (a sum of -0.0 alone is +0.0) and hands on NaN and inf; float min / max skip NaNs (all
+ * NaN, or n == 0: the identity, +inf / -inf); int32 sums wrap mod 2^32; n == 0 gives the identity (0, INT32_MAX,
+ * INT32_MIN). */
+int pcmx_reduce_f32_grid(const float* x, long long n, int op, float* out, void* workspace, int max_blocks, hipStream_t s);
+int pcmx_reduce_i32_grid(const int32_t* x, long long n, int op, int32_t* out, void* workspace, int max_blocks, hipStream_t s);
+int pcmx_dot_f32_grid(const float* a, const float* b, long long n, float* out, void* workspace, int max_blocks, hipStream_t s);
 
 /* ---------------------------------------------------------------- prefix scan */
 long long pcmx_scan_workspace_bytes(long long n);

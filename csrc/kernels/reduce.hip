@@ -36,6 +36,17 @@ __device__ __forceinline__ T comb(T a, T b) {
     return b > a ? b : a;
 }
 
+// One float4 into an accumulator. A sum keeps its tree, (x + y) + (z + w). A float min / max takes the components one
+// after the other: comb skips a NaN only as its right-hand operand (`b < a` is false), and a tree hands a NaN in x or
+// z on as the left-hand one, where it hides y, z and w (or w) from the result. The accumulator itself never is a NaN.
+template <class T, int OP, class V>
+__device__ __forceinline__ T fold4(T acc, const V& v) {
+    if constexpr (OP == 0 || !std::is_same<T, float>::value)
+        return comb<T, OP>(acc, comb<T, OP>(comb<T, OP>(v.x, v.y), comb<T, OP>(v.z, v.w)));
+    else
+        return comb<T, OP>(comb<T, OP>(comb<T, OP>(comb<T, OP>(acc, v.x), v.y), v.z), v.w);
+}
+
 template <class T, int OP>
 __device__ __forceinline__ T block_reduce(T v, T* lds) {
     v = pcmx::wave_reduce<T, OP>(v);
@@ -77,8 +88,7 @@ __global__ __launch_bounds__(kThreads) void reduce_pass1(const T* __restrict__ x
             }
         }
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u)
-            acc[u] = comb<T, OP>(acc[u], comb<T, OP>(comb<T, OP>(v[u].x, v[u].y), comb<T, OP>(v[u].z, v[u].w)));
+        for (int u = 0; u < kUnroll; ++u) acc[u] = fold4<T, OP>(acc[u], v[u]);
     }
     for (; i < n4; i += kThreads) {
         V v = x4[i];
@@ -86,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void reduce_pass1(const T* __restrict__ x
             V w = y4[i];
             v.x *= w.x, v.y *= w.y, v.z *= w.z, v.w *= w.w;
         }
-        acc[0] = comb<T, OP>(acc[0], comb<T, OP>(comb<T, OP>(v.x, v.y), comb<T, OP>(v.z, v.w)));
+        acc[0] = fold4<T, OP>(acc[0], v);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         long long t = (n4 << 2) + threadIdx.x;
@@ -135,18 +145,24 @@ __global__ __launch_bounds__(kThreads) void reduce_pass2(const T* __restrict__ p
     if (threadIdx.x == 0) out[0] = (T)r;
 }
 
-inline int pass1_blocks(long long n) {
+// Pass-1 grid: one block per kUnroll float4 per thread, at least one, at most `cap` (then the blocks grid-stride).
+inline int pass1_blocks(long long n, int cap) {
     long long b = ((n >> 2) + (long long)kThreads * kUnroll - 1) / ((long long)kThreads * kUnroll);
     if (b < 1) b = 1;
-    if (b > kMaxBlocks) b = kMaxBlocks;
+    if (b > cap) b = cap;
     return (int)b;
 }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// The one launch path: the production entries pass kMaxBlocks, the *_grid entries (tests: a small cap reaches the
+// second and third grid-stride trip at a few hundred thousand elements) any cap in 1..kMaxBlocks. The workspace
+// size does not depend on the cap, which only lowers the block count.
 template <class T, bool PROD>
-int launch_reduce(const T* x, const T* y, long long n, int op, T* out, void* ws, hipStream_t s) {
-    if (n < 0 || !aligned16(x) || (PROD && !aligned16(y)) || ws == nullptr || !aligned16(ws)) return -1;
-    const int nb = pass1_blocks(n);
+int launch_reduce(const T* x, const T* y, long long n, int op, T* out, void* ws, int max_blocks, hipStream_t s) {
+    if (n < 0 || !aligned16(x) || (PROD && !aligned16(y)) || ws == nullptr || !aligned16(ws) || max_blocks < 1 ||
+        max_blocks > kMaxBlocks)
+        return PCMX_ERR_ARG;
+    const int nb = pass1_blocks(n, max_blocks);
     T* partials = reinterpret_cast<T*>(ws);
     switch (op) {
         case PCMX_OP_SUM:
@@ -162,20 +178,31 @@ int launch_reduce(const T* x, const T* y, long long n, int op, T* out, void* ws,
             reduce_pass2<T, 2><<<1, kThreads, 0, s>>>(partials, nb, out);
             break;
         default:
-            return -1;
+            return PCMX_ERR_ARG;
     }
     return (int)hipGetLastError();
 }
 }  // namespace
 
-extern "C" long long pcmx_reduce_workspace_bytes(long long n) { return (long long)pass1_blocks(n) * 8; }
+extern "C" long long pcmx_reduce_workspace_bytes(long long n) { return (long long)pass1_blocks(n, kMaxBlocks) * 8; }
 
+extern "C" int pcmx_reduce_f32_grid(const float* x, long long n, int op, float* out, void* ws, int max_blocks, hipStream_t s) {
+    return launch_reduce<float, false>(x, x, n, op, out, ws, max_blocks, s);
+}
+extern "C" int pcmx_reduce_i32_grid(const int32_t* x, long long n, int op, int32_t* out, void* ws, int max_blocks,
+                                    hipStream_t s) {
+    return launch_reduce<int32_t, false>(x, x, n, op, out, ws, max_blocks, s);
+}
+extern "C" int pcmx_dot_f32_grid(const float* a, const float* b, long long n, float* out, void* ws, int max_blocks,
+                                 hipStream_t s) {
+    return launch_reduce<float, true>(a, b, n, PCMX_OP_SUM, out, ws, max_blocks, s);
+}
 extern "C" int pcmx_reduce_f32(const float* x, long long n, int op, float* out, void* ws, hipStream_t s) {
-    return launch_reduce<float, false>(x, x, n, op, out, ws, s);
+    return pcmx_reduce_f32_grid(x, n, op, out, ws, kMaxBlocks, s);
 }
 extern "C" int pcmx_reduce_i32(const int32_t* x, long long n, int op, int32_t* out, void* ws, hipStream_t s) {
-    return launch_reduce<int32_t, false>(x, x, n, op, out, ws, s);
+    return pcmx_reduce_i32_grid(x, n, op, out, ws, kMaxBlocks, s);
 }
 extern "C" int pcmx_dot_f32(const float* a, const float* b, long long n, float* out, void* ws, hipStream_t s) {
-    return launch_reduce<float, true>(a, b, n, PCMX_OP_SUM, out, ws, s);
+    return pcmx_dot_f32_grid(a, b, n, out, ws, kMaxBlocks, s);
 }

@@ -70,7 +70,11 @@ def copy_(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
 
 
 def dot(a: torch.Tensor, b: torch.Tensor, n_threads: int = 0) -> torch.Tensor:
-    """sum(a*b) as a 0-d float32 tensor (f64 host accumulation / f64 final fold on the GPU)."""
+    """sum(a*b) as a 0-d float32 tensor (f64 host accumulation / f64 final fold on the GPU).
+
+    On the GPU the products are summed as ``reduce`` sums float32: from +0.0 (a dot of -0.0 products is +0.0), NaN and
+    inf are handed on, the same bits on every call and stream; empty operands give +0.0. Any view is accepted
+    (strided or not 16-byte aligned operands are copied first; the inputs are never written)."""
     if a.is_cuda:
         return ops().dot(a, b)
     a, b = _f32(a, "a"), _f32(b, "b")
@@ -81,7 +85,18 @@ def reduce(x: torch.Tensor, op: str = "sum", dim: int | None = None, keepdim: bo
            chunk: int | None = None) -> torch.Tensor:
     """Global reduction of a float32/int32 tensor to a 0-d tensor (op in sum/min/max). dim=int: the reduction of every
     row along dim, torch's shape (dim removed, or kept with size 1 under keepdim); keepdim, route and chunk go with dim
-    (the along-a-dimension section below)."""
+    (the along-a-dimension section below).
+
+    The global reduction on the GPU (two passes, the second folds the block partials in f64 / int64 in a fixed order:
+    the same bits on every call and stream):
+      * a float32 sum starts from +0.0, so a sum of -0.0 alone is +0.0; it hands on NaN and inf, and +inf with -inf
+        gives NaN;
+      * float32 min and max skip NaNs wherever they stand; an all-NaN input gives the identity, +inf for min and -inf
+        for max (torch.min / max hand the NaN on);
+      * int32 sums wrap mod 2^32 (the block partials wrap in int32, their int64 fold is cast back; the CPU path casts
+        an int64 sum back and agrees); int32 min and max are exact, INT32_MIN / INT32_MAX inputs included;
+      * numel() == 0 gives the identity: +0.0, +inf, -inf (int32: 0, INT32_MAX, INT32_MIN);
+      * any view is accepted (strided or not 16-byte aligned input is copied first; the input is never written)."""
     if dim is not None:
         return _axis_reduce(x, op, dim, keepdim, route, chunk)
     if keepdim or route is not None or chunk is not None:
@@ -107,6 +122,9 @@ def scan(x: torch.Tensor, exclusive: bool = False, init: torch.Tensor | None = N
     stream and raises if this (or an earlier unchecked) scan on it gave up a look-back (scan_check).
     ``dim=int``: the running op (sum, min, max; float32 or int32) of every row along dim, x's shape; op, out, route
     and chunk go with dim (the along-a-dimension section below).
+    A multi-dimensional or strided x is scanned in its logical (row-major flattened) order and the result has x's
+    shape; numel() == 0 returns an empty tensor. A NaN or inf at position p reaches every output from p on (exclusive:
+    after p) and leaves the outputs before it as they are without it; +inf and a later -inf give NaN from the second on.
     """
     if dim is not None:
         return _axis_scan(x, op, exclusive, init, check, dim, out, route, chunk)
