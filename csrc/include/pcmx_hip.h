@@ -415,6 +415,47 @@ int pcmx_segment_sort_b32(const void* keys_in, void* keys_out, const void* vals_
                           const int32_t* offsets, long long S, int key_type, int mode, int descending, int begin_bit,
                           int end_bit, void* workspace, hipStream_t s);
 
+/* ---------------------------------------------------------------- argmin / argmax (flat, along a dimension, ragged) */
+/* Where the extremum is, and its value (csrc/kernels/argreduce.hip). key_type is PCMX_KEY_F32 or PCMX_KEY_I32, op is
+ * PCMX_OP_MIN or PCMX_OP_MAX. One rule for the three forms: a NaN beats every number under both ops (torch's rule for
+ * argmax / argmin / max(dim) / min(dim), NOT the NaN-skipping rule of pcmx_reduce_*); otherwise the numerically largest
+ * (smallest) element wins with -0.0 == +0.0; among equal winners and among NaNs the lowest position wins; the value
+ * written is the input element at that position, bit for bit. Positions are int32. The result depends on the data
+ * only, never on the route, the chunk, the grid or timing. value_out or index_out may be NULL (not both): that output
+ * is not written. x and the workspace 16-B aligned (the segment form: x and offsets 4-B), the outputs 4-B aligned and
+ * overlapping neither an input nor each other. PCMX_ERR_ARG with nothing launched: another key type or op
+ * (PCMX_OP_SUM), a NULL or misaligned required pointer, a negative extent, 2^31 elements or more, a route or chunk
+ * that does not fit the shape, max_blocks outside 1..16384.
+ *
+ * Flat: two launches, reduce.hip's shape (the first pass's grid capped at max_blocks, 16384 for the plain entry; the
+ * blocks then grid-stride; one block folds the 8-byte block partials and reads the value). index_out[0] is the position
+ * in x[0, n); n == 0 gives -1 and the identity (-inf / INT32_MIN for MAX, +inf / INT32_MAX for MIN). The workspace is
+ * pcmx_arg_reduce_workspace_bytes(n) whatever the cap. */
+long long pcmx_arg_reduce_workspace_bytes(long long n);
+int pcmx_arg_reduce_b32(const void* x, long long n, int key_type, int op, void* value_out, int32_t* index_out, void* workspace,
+                        hipStream_t s);
+int pcmx_arg_reduce_b32_grid(const void* x, long long n, int key_type, int op, void* value_out, int32_t* index_out,
+                             void* workspace, int max_blocks, hipStream_t s);
+/* Along the middle extent of a contiguous [outer, n, inner] tensor, read where it lies: value_out / index_out are
+ * [outer, inner], the position is the position along n. route and chunk as for pcmx_axis_reduce_* (the reduce halves of
+ * the same routes; 0 picks by the PCMX_AXIS_* borders of a reduce, which were measured for 4-byte reductions and are
+ * not measured for the 8-byte partials used here). n == 0 with outer and inner above 0 is PCMX_ERR_ARG; outer == 0 or
+ * inner == 0 returns 0 and touches nothing. outer * n * inner < 2^31. The workspace (pcmx_axis_arg_workspace_bytes, one
+ * call in flight per workspace) may be NULL for the routes that are not split. */
+long long pcmx_axis_arg_workspace_bytes(long long outer, long long n, long long inner);
+int pcmx_axis_arg_reduce_b32(const void* x, void* value_out, int32_t* index_out, long long outer, long long n, long long inner,
+                             int key_type, int op, int route, long long chunk, void* workspace, hipStream_t s);
+/* Over the segments [offsets[j], offsets[j+1]) of x, j < S, offsets as for pcmx_segment_reduce_* (same PRECONDITION,
+ * not checked: offsets that break it give an unspecified result, but every load and store stays inside x[0, n),
+ * offsets[0, S], the outputs' [0, S) and the workspace). index_out[j] is the FLAT position in x (offsets[j] <=
+ * index_out[j] < offsets[j+1]); an empty segment gives -1 and the identity as its value. The merge-based scheme of
+ * ragged.hip with (key, flat index) words: four launches, no block waits for another. n + S < 2^31; S == 0 returns 0
+ * and touches nothing; x may be NULL when n == 0. Workspace: pcmx_segment_arg_workspace_bytes(n, S), one call in
+ * flight per workspace. */
+long long pcmx_segment_arg_workspace_bytes(long long n, long long S);
+int pcmx_segment_arg_reduce_b32(const void* x, long long n, const int32_t* offsets, long long S, int key_type, int op,
+                                void* value_out, int32_t* index_out, void* workspace, hipStream_t s);
+
 /* ---------------------------------------------------------------- SGEMM (fp32 MFMA) */
 /* C = alpha*A*B + beta*C, row-major. Fast path needs M%256==0, N%256==0 (or %128 for the small-tile
  * kernel), K%32==0, 16-B aligned rows; anything else returns -1 (the torch layer pads). */

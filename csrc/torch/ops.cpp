@@ -989,6 +989,88 @@ at::Tensor segment_reduce(const at::Tensor& x, const at::Tensor& offsets, int64_
     return head;
 }
 
+// ---------------------------------------------------------------- argmin / argmax (csrc/kernels/argreduce.hip)
+// (values, indices) of op (PCMX_OP_MIN / PCMX_OP_MAX) for float32 / int32; an output that is not wanted is not written
+// by the kernels and comes back as an empty tensor. Shapes, op, route and chunk are checked in Python and again by the C
+// entry points; workspaces come from torch's allocator on the current stream; nothing synchronises.
+int arg_key_type(const at::Tensor& x, const char* what) {
+    TORCH_CHECK(x.is_cuda(), what, ": GPU tensor expected");
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kInt, what, ": x has dtype ", x.scalar_type(),
+                ", expected float32 or int32");
+    return x.scalar_type() == at::kFloat ? PCMX_KEY_F32 : PCMX_KEY_I32;
+}
+
+// 0-d outputs; the index into the row-major flattened tensor
+std::tuple<at::Tensor, at::Tensor> arg_reduce(const at::Tensor& x, int64_t op, bool want_values, bool want_indices) {
+    const int kt = arg_key_type(x, "arg_reduce");
+    TORCH_CHECK(x.numel() > 0, "arg_reduce: no extremum of an empty tensor");
+    TORCH_CHECK(want_values || want_indices, "arg_reduce: nothing to compute");
+    const at::DeviceGuard g(x.device());
+    at::Tensor xc = aligned_contig(x);
+    at::Tensor vals = want_values ? at::empty({}, x.options()) : at::empty({0}, x.options());
+    at::Tensor idx = want_indices ? at::empty({}, x.options().dtype(at::kInt)) : at::empty({0}, x.options().dtype(at::kInt));
+    auto ws = workspace(x, pcmx_arg_reduce_workspace_bytes(xc.numel()));
+    check_rc(pcmx_arg_reduce_b32(xc.data_ptr(), xc.numel(), kt, (int)op, want_values ? vals.data_ptr() : nullptr,
+                                 want_indices ? idx.data_ptr<int32_t>() : nullptr, ws.data_ptr(), cur_stream(x)),
+             "arg_reduce");
+    return {vals, idx};
+}
+
+// x is the [outer, n, inner] view; outputs [outer, inner], the position along n
+std::tuple<at::Tensor, at::Tensor> axis_arg_reduce(const at::Tensor& x, int64_t op, int64_t route, int64_t chunk, bool want_values,
+                                                   bool want_indices) {
+    const int kt = arg_key_type(x, "axis_arg_reduce");
+    TORCH_CHECK(x.dim() == 3, "axis_arg_reduce: expected a 3-D [outer, n, inner] tensor, got ", x.dim(), " dimensions");
+    TORCH_CHECK(want_values || want_indices, "axis_arg_reduce: nothing to compute");
+    const at::DeviceGuard g(x.device());
+    at::Tensor xc = aligned_contig(x);
+    const int64_t outer = xc.size(0), n = xc.size(1), inner = xc.size(2);
+    TORCH_CHECK(n > 0, "axis_arg_reduce: no extremum along an empty dimension");
+    at::Tensor vals = want_values ? at::empty({outer, inner}, x.options()) : at::empty({0}, x.options());
+    at::Tensor idx = want_indices ? at::empty({outer, inner}, x.options().dtype(at::kInt)) : at::empty({0}, x.options().dtype(at::kInt));
+    if (outer * inner == 0) return {vals, idx};
+    auto ws = workspace(x, pcmx_axis_arg_workspace_bytes(outer, n, inner));
+    check_rc(pcmx_axis_arg_reduce_b32(xc.data_ptr(), want_values ? vals.data_ptr() : nullptr,
+                                      want_indices ? idx.data_ptr<int32_t>() : nullptr, outer, n, inner, kt, (int)op, (int)route,
+                                      chunk, ws.data_ptr(), cur_stream(x)),
+             "axis_arg_reduce");
+    return {vals, idx};
+}
+
+// [S] outputs; the FLAT index into x.flatten(), -1 and the identity for an empty segment. out_values / out_indices
+// (1-D, contiguous, at least S elements) are written in [:S] only and returned as their [:S].
+std::tuple<at::Tensor, at::Tensor> segment_arg_reduce(const at::Tensor& x, const at::Tensor& offsets, int64_t op, bool want_values,
+                                                      bool want_indices, const c10::optional<at::Tensor>& out_values,
+                                                      const c10::optional<at::Tensor>& out_indices) {
+    const int kt = arg_key_type(x, "segment_arg_reduce");
+    TORCH_CHECK(x.is_contiguous(), "segment_arg_reduce: x must be contiguous");
+    TORCH_CHECK(want_values || want_indices, "segment_arg_reduce: nothing to compute");
+    const at::DeviceGuard g(x.device());
+    at::Tensor oc = segment_offsets(offsets, x, "segment_arg_reduce");
+    const int64_t n = x.numel(), S = oc.numel() - 1;
+    TORCH_CHECK(n + S < (1LL << 31), "segment_arg_reduce: elements and segments together must be fewer than 2^31");
+    auto dest = [&](const c10::optional<at::Tensor>& out, bool want, at::ScalarType dt, const char* name) {
+        if (!want) return at::empty({0}, x.options().dtype(dt));
+        if (!(out.has_value() && out->defined())) return at::empty({S}, x.options().dtype(dt));
+        check_gpu(*out, name, dt);
+        TORCH_CHECK(out->device() == x.device() && out->dim() == 1 && out->is_contiguous() && out->numel() >= S,
+                    "segment_arg_reduce: ", name, " must be 1-D, contiguous, on x's device, with at least ", S, " elements");
+        TORCH_CHECK(!(S && overlaps(*out, x)) && !overlaps(*out, oc), "segment_arg_reduce: ", name, " must not overlap an input");
+        return out->narrow(0, 0, S);
+    };
+    at::Tensor vals = dest(out_values, want_values, x.scalar_type(), "out_values");
+    at::Tensor idx = dest(out_indices, want_indices, at::kInt, "out_indices");
+    if (S != 0) {
+        at::Tensor xc = x.view(-1);
+        auto ws = workspace(x, pcmx_segment_arg_workspace_bytes(n, S));
+        check_rc(pcmx_segment_arg_reduce_b32(n ? xc.data_ptr() : nullptr, n, oc.data_ptr<int32_t>(), S, kt, (int)op,
+                                             want_values ? vals.data_ptr() : nullptr,
+                                             want_indices ? idx.data_ptr<int32_t>() : nullptr, ws.data_ptr(), cur_stream(x)),
+                 "segment_arg_reduce");
+    }
+    return {vals, idx};
+}
+
 // uint8 [n]: 1 at every offsets[j] < n, 0 elsewhere: the head flags segmented_scan takes
 at::Tensor segment_heads(const at::Tensor& offsets, int64_t n, const at::Tensor& like) {
     TORCH_CHECK(like.is_cuda(), "segment_heads: the values must be a GPU tensor");
@@ -1616,6 +1698,9 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("searchsorted(Tensor sorted_sequence, Tensor values, bool right=False, bool descending=False, bool values_sorted=False, Tensor(a!)? out=None) -> Tensor");
     m.def("segment_reduce(Tensor x, Tensor offsets, int op, Tensor(a!)? out=None) -> Tensor");
     m.def("segment_heads(Tensor offsets, int n, Tensor like) -> Tensor");
+    m.def("arg_reduce(Tensor x, int op, bool want_values=True, bool want_indices=True) -> (Tensor, Tensor)");
+    m.def("axis_arg_reduce(Tensor x, int op, int route=0, int chunk=0, bool want_values=True, bool want_indices=True) -> (Tensor, Tensor)");
+    m.def("segment_arg_reduce(Tensor x, Tensor offsets, int op, bool want_values=True, bool want_indices=True, Tensor(a!)? out_values=None, Tensor(b!)? out_indices=None) -> (Tensor, Tensor)");
     m.def("segment_sort(Tensor keys, Tensor? values, Tensor offsets, int mode, bool descending=False, int begin_bit=0, int end_bit=32, bool want_keys=True) -> (Tensor, Tensor, Tensor)");
     m.def("sgemm(Tensor a, Tensor b, int variant=-1) -> Tensor");
     m.def("sgemm_out(Tensor a, Tensor b, Tensor(a!) c, float alpha=1., float beta=0., int variant=-1) -> Tensor(a!)");
@@ -1682,6 +1767,9 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("searchsorted", searchsorted);
     m.impl("segment_reduce", segment_reduce);
     m.impl("segment_heads", segment_heads);
+    m.impl("arg_reduce", arg_reduce);
+    m.impl("axis_arg_reduce", axis_arg_reduce);
+    m.impl("segment_arg_reduce", segment_arg_reduce);
     m.impl("segment_sort", segment_sort);
     m.impl("sgemm", sgemm);
     m.impl("sgemm_out", sgemm_out);

@@ -1622,10 +1622,94 @@ class SegSort(Ragged):
         return rep
 
 
+class ArgReduce(Workload):
+    """argmin / argmax (csrc/kernels/argreduce.hip) per GPU: form "flat" (ops.arg_reduce(x, op) on n elements), "dim"
+    (ops.arg_reduce(x, op, dim=1) on an [outer, n, inner] tensor, route and chunk the op's) or "segments"
+    (ops.segment_arg_reduce(x, offsets, op) on n elements, dist and mean_len placing the borders as in the ragged
+    workload). op max / min; dtype f32 (multiples of 1/4 from a normal distribution, so longer rows hold their
+    extremum several times) or i32 (the full range). No communication (weak scaling)."""
+
+    FORMS = ("flat", "dim", "segments")
+
+    def __init__(self, ctx, form="flat", op="max", dtype="f32", n=1 << 28, outer=1 << 14, inner=1, route=None, chunk=None,
+                 mean_len=100.0, dist="uniform", **_):
+        if form not in self.FORMS:
+            raise ValueError(f"argreduce form {form!r}: one of {self.FORMS}")
+        if op not in ops.vector.ARG_OPS:
+            raise ValueError(f"argreduce op {op!r}: one of {ops.vector.ARG_OPS}")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"argreduce dtype {dtype!r}: f32 or i32")
+        n, outer, inner = int(n), int(outer), int(inner)
+        if min(outer, n, inner) < 1:
+            raise ValueError(f"argreduce n = {n}, outer = {outer}, inner = {inner}: every extent at least 1")
+        if form != "dim" and (route is not None or chunk is not None):
+            raise ValueError("argreduce: route and chunk go with form 'dim'")
+        super().__init__(ctx, {"form": form, "op": op, "dtype": dtype, "n": n}, "argreduce", "GB/s")
+        self.form, self.op, self.route, self.chunk, self.offsets = form, op, route, chunk, None
+        shape = (n,)
+        if form == "dim":
+            shape = (outer, n, inner)
+            self.cfg.update({"outer": outer, "inner": inner, "route": route, "chunk": chunk})
+            _axis_plan("reduce", route, chunk, outer, n, inner, "argreduce")  # a route that cannot take the shape raises here
+        elif form == "segments":
+            self.cfg.update({"mean_len": float(mean_len), "dist": dist})
+            self.offsets = Ragged(ctx, n, mean_len, dist, "max", "i32").offsets
+        g = torch.Generator(device=ctx.device).manual_seed(23000 + ctx.rank)
+        if dtype == "f32":
+            self.x = torch.round(torch.randn(shape, device=ctx.device, generator=g) * 4) / 4
+        else:
+            self.x = torch.randint(-(1 << 31), 1 << 31, shape, device=ctx.device, generator=g, dtype=torch.int64).to(torch.int32)
+        self.out = None
+
+    def _run(self, x, offsets):
+        if self.form == "flat":
+            return ops.arg_reduce(x, self.op)
+        if self.form == "dim":
+            return ops.arg_reduce(x, self.op, dim=1, route=self.route, chunk=self.chunk)
+        return ops.segment_arg_reduce(x, offsets, self.op)
+
+    def step(self):
+        self.out = self._run(self.x, self.offsets)
+
+    def torch_step(self):
+        """The torch call this replaces (the vendor bar); torch has no arg form of segment_reduce."""
+        if self.form == "flat":
+            return torch.argmax(self.x) if self.op == "max" else torch.argmin(self.x)
+        if self.form == "dim":
+            return (torch.max if self.op == "max" else torch.min)(self.x, 1)
+        raise NotImplementedError("torch has no argmax over ragged segments")
+
+    def results(self) -> int:
+        return 1 if self.form == "flat" else (self.x.shape[0] * self.x.shape[2] if self.form == "dim" else self.offsets.numel() - 1)
+
+    def work_per_step(self):
+        # the bytes a caller sees move: the input (and the offsets) read once, a value and an index per result written
+        offs = 0 if self.offsets is None else self.offsets.numel()
+        return float(4 * (self.x.numel() + offs + 2 * self.results()))
+
+    def check(self, reduce: bool = True):
+        """Values (as bit patterns) and indices of the timed step against the host path on a host copy. Local only."""
+        ref = self._run(self.x.cpu(), None if self.offsets is None else self.offsets.cpu())
+        out = [t.cpu() for t in self.out]
+        ok = all(a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+                 for a, b in zip(out, ref))
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"elements_checked": 2 * self.results(), "exact_vs_host": True, "check_passed": ok}
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gelems_per_s"] = self.ctx.world * self.x.numel() * steps / seconds / 1e9
+        rep["results"] = self.results()
+        return rep
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
              "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
-             "merge": Merge, "rowsort": RowSort, "axis": Axis, "ragged": Ragged, "segsort": SegSort}
+             "merge": Merge, "rowsort": RowSort, "axis": Axis, "ragged": Ragged, "segsort": SegSort,
+             "argreduce": ArgReduce}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

@@ -16,6 +16,9 @@ from .vector import (CMP_CODES, OP_CODES, argsort, axpy_, bincount, bucketize, c
 # segment_sort_keys / segment_sort / segment_argsort / segment_sort_by_key sort inside the same ragged segments
 # (csrc/kernels/segsort.hip; SEGSORT_CLASS_LIMITS, SEGSORT_MAX_LEN, SEGSORT_GRID_MULT)
 from .vector import segment_argsort, segment_sort, segment_sort_by_key, segment_sort_keys
+# arg_reduce / argmax / argmin (flat or dim=int) and segment_arg_reduce / segment_argmax / segment_argmin say where the
+# extremum is (csrc/kernels/argreduce.hip; ARG_BLOCK, ARG_MAX_BLOCKS)
+from .vector import arg_reduce, argmax, argmin, segment_arg_reduce, segment_argmax, segment_argmin
 
 __all__ = [
     "sgemm", "sgemm_out", "sgemm_simt", "sgemm_naive_host",
@@ -33,4 +36,5 @@ __all__ = [
     "merge_keys", "merge", "merge_by_key", "searchsorted", "bucketize",
     "segment_reduce", "segment_scan",
     "segment_sort_keys", "segment_sort", "segment_argsort", "segment_sort_by_key",
+    "arg_reduce", "argmax", "argmin", "segment_arg_reduce", "segment_argmax", "segment_argmin",
 ]

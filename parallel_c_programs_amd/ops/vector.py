@@ -1840,3 +1840,190 @@ def segment_sort_by_key(keys: torch.Tensor, values: torch.Tensor, offsets: torch
     and max_len as for segment_sort_keys (one sync of 16 bytes; none with max_len <= SEGSORT_MAX_LEN, a broken promise
     giving an unspecified result in bounds)."""
     return _segment_sort(keys, values, offsets, "pairs", descending, bits, validate, max_len, route, "segment_sort_by_key")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# argmin / argmax: flat, along a dimension and over ragged segments (csrc/kernels/argreduce.hip; no counterpart in the
+# reference programs). One rule for all forms, float32 and int32:
+#  1. a NaN beats every number, for max AND min: torch's rule for argmax / argmin / max(dim) / min(dim) and the rule of
+#     reduce(dim=). It is NOT the rule of the flat reduce(x, "max"), which skips NaNs;
+#  2. otherwise the numerically largest (smallest) element wins; -0.0 and +0.0 are equal;
+#  3. among equal winners, and among several NaNs, the lowest position wins;
+#  4. the value returned is the input element at the returned position, bit for bit (the sign of a zero, a NaN's
+#     payload).
+# Indices are int32. On the GPU the element of the reduction is the (ordered key, ~position) pair packed into 64 bits
+# under an unsigned max: associative and commutative, so the result depends on the data only, never on the route, the
+# chunk, the grid, the row's place in the tensor or timing, and every result can be tested for equality.
+#  * flat: two launches, each element read once (ARG_BLOCK elements per block and trip, at most ARG_MAX_BLOCKS blocks).
+#  * dim=: the reduce halves of the routes of reduce(dim=) under the same names, with 8-byte partials. The default
+#    route is _axis_route("reduce", ...) unchanged: those borders were measured for 4-byte reductions and are NOT
+#    MEASURED for pairs.
+#  * segments: the merge-path tiles, carry scan and fix-up of segment_reduce (RAGGED_TILE path steps per block).
+# Nothing synchronises.
+#  * Measured on one MI355X (scripts/argreduce_lab.py, profiles/r23_argreduce/README.md; op max, median ms). Flat at 2^28
+#    float32: 0.181 against torch.argmax 0.423, topk(x, 1) 1.325 (the route until now), reduce(x, "max") 0.163 and copy_
+#    of the same bytes 0.175. Along a dimension, ours / torch.max(x, dim): [2^20, 32] 0.053 / 0.203, [8, 2^24] 0.120 /
+#    5.90, [2^20, 64] along dim 0 0.102 / 0.228; 0.57x-0.97x of reduce(dim=). SLOWER than torch on the block route:
+#    [16384, 4096] 0.071 against 0.055 ms, [1024, 32768] 0.036 against 0.031, int32 [64, 1024, 1024] along dim 1 0.078
+#    against 0.065. Segments at 2^28: 0.46-0.55 ms from one segment to mean length 100, 0.81 / 1.45 ms at length 4 / 1:
+#    SLOWER than segment_reduce(x, offsets, "max") in every case (0.81x-0.87x), 2.2x-3.1x the copy floor.
+ARG_OPS = ("min", "max")
+ARG_BLOCK = 4096          # csrc/kernels/argreduce.hip: elements per block and grid-stride trip of the flat first pass
+ARG_MAX_BLOCKS = 16384    # ... and the cap of its grid
+
+
+def _check_arg(x: torch.Tensor, op, name: str) -> None:
+    if op not in ARG_OPS:
+        raise ValueError(f"{name}: op must be 'min' or 'max', got {op!r}")
+    if x.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name}: x must be float32 or int32, got {x.dtype}")
+    if x.numel() >= 1 << 31:
+        raise ValueError(f"{name}: x has {x.numel()} elements; indices are int32 (fewer than 2^31)")
+
+
+def _arg_key(x: torch.Tensor, op: str) -> torch.Tensor:
+    """int64 keys whose order is the rule's: radix_key.h's ordered key (-0.0 == +0.0, every NaN one key above +inf),
+    flipped for min with the NaN key kept on top. The host path's statement of rules 1 and 2."""
+    b = x.contiguous().view(torch.int32).long() & 0xFFFFFFFF
+    nan = None
+    if x.dtype == torch.float32:
+        a = b & 0x7FFFFFFF
+        nan = a > 0x7F800000
+        k = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b | 0x80000000)
+        k = torch.where(a == 0, torch.full_like(k, 0x80000000), k)
+        k = torch.where(nan, torch.full_like(k, 0xFFFFFFFF), k)
+    else:
+        k = b ^ 0x80000000
+    if op == "min":
+        k = 0xFFFFFFFF - k
+        if nan is not None:
+            k = torch.where(nan, torch.full_like(k, 0xFFFFFFFF), k)
+    return k
+
+
+def _arg_identity(dtype: torch.dtype, op: str):
+    return _SCAN_IDENTITY[op][0 if dtype == torch.float32 else 1]
+
+
+def _host_axis_arg(x3: torch.Tensor, op: str):
+    """(values, int32 positions along n) of the [outer, n, inner] tensor on the host: the first position of the extreme
+    key, the value gathered as bits."""
+    n = x3.shape[1]
+    key = _arg_key(x3, op)
+    pos = torch.arange(n).view(1, n, 1)
+    idx = torch.where(key == key.amax(1, keepdim=True), pos, n).amin(1)
+    vals = x3.contiguous().view(torch.int32).gather(1, idx.unsqueeze(1)).squeeze(1).view(x3.dtype)
+    return vals, idx.int()
+
+
+def _host_segment_arg(xf: torch.Tensor, offsets: torch.Tensor, op: str):
+    n, s = xf.numel(), offsets.numel() - 1
+    vals = torch.full((s,), _arg_identity(xf.dtype, op), dtype=xf.dtype)
+    idx = torch.full((s,), -1, dtype=torch.int32)
+    if s == 0 or n == 0:
+        return vals, idx
+    o = offsets.long()
+    lo, hi = int(o[0]), int(o[-1])
+    if hi <= lo:
+        return vals, idx
+    pos = torch.arange(lo, hi)
+    ids = torch.searchsorted(o[1:].contiguous(), pos, right=True)
+    key = _arg_key(xf[lo:hi], op)
+    top = torch.full((s,), -1, dtype=torch.int64).scatter_reduce(0, ids, key, "amax", include_self=True)
+    first = torch.full((s,), n, dtype=torch.int64).scatter_reduce(0, ids, torch.where(key == top[ids], pos, n), "amin",
+                                                                  include_self=True)
+    hit = first < n
+    idx[hit] = first[hit].int()
+    vb = vals.view(torch.int32)
+    vb[hit] = xf.view(torch.int32)[first[hit]]
+    return vals, idx
+
+
+def _arg_reduce(x: torch.Tensor, op, dim, keepdim, route, chunk, want_values: bool, want_indices: bool, name: str):
+    _check_arg(x, op, name)
+    if dim is None:
+        if keepdim or route is not None or chunk is not None:
+            raise ValueError(f"{name}: keepdim, route and chunk are for the form along a dimension: they need dim=")
+        if x.numel() == 0:
+            raise ValueError(f"{name}: an empty tensor has no extremum")
+        if x.is_cuda:
+            v, i = ops().arg_reduce(x, OP_CODES[op], want_values, want_indices)
+        else:
+            v, i = _host_axis_arg(x.reshape(1, -1, 1), op)
+            v, i = v.reshape(()), i.reshape(())
+        return (v if want_values else None), (i if want_indices else None)
+    outer, n, inner, d = _axis_view(x, dim, op, name)
+    if n == 0:
+        raise ValueError(f"{name}: dimension {d} has size 0: no extremum")
+    code, chunk = _axis_plan("reduce", route, chunk, outer, n, inner, name)  # borders NOT MEASURED for 8-byte pairs
+    x3 = x.contiguous().view(outer, n, inner)
+    if x.is_cuda:
+        v, i = ops().axis_arg_reduce(x3, OP_CODES[op], code, chunk, want_values, want_indices)
+    else:
+        v, i = _host_axis_arg(x3, op)
+    shape = list(x.shape)
+    shape[d:d + 1] = [1] if keepdim else []
+    return (v.reshape(shape) if want_values else None), (i.reshape(shape) if want_indices else None)
+
+
+def arg_reduce(x: torch.Tensor, op: str, dim: int | None = None, keepdim: bool = False, route: str | None = None,
+               chunk: int | None = None):
+    """(values, indices) of the extremum of a float32 / int32 tensor, op "max" or "min"; indices are int32.
+    dim=None: 0-d tensors, the index into the row-major flattened tensor. dim=int: torch.max(x, dim, keepdim)'s shapes,
+    the position along dim; route and chunk as for reduce(dim=) (the default route is that of a reduce: its borders are
+    not measured for the 8-byte partials used here).
+
+    A NaN beats every number under BOTH ops (torch.argmax / argmin / max(dim) / min(dim), and reduce(dim=); not the
+    NaN-skipping rule of the flat reduce(x, "max")); -0.0 == +0.0; among equal winners and among NaNs the lowest
+    position wins; the value is the input element at that position, bit for bit. The result depends on the data only,
+    never on the route, the chunk or timing. Any view is accepted (strided or misaligned input is copied first; the
+    input is never written). ValueError: another op, an empty tensor or dimension, keepdim / route / chunk without
+    dim, a route or chunk that does not fit; TypeError: another dtype. Does not synchronise."""
+    return _arg_reduce(x, op, dim, keepdim, route, chunk, True, True, "arg_reduce")
+
+
+def argmax(x: torch.Tensor, dim: int | None = None, keepdim: bool = False) -> torch.Tensor:
+    """The indices of arg_reduce(x, "max", dim, keepdim) alone (int32; torch.argmax's positions, NaN first); no value
+    is written."""
+    return _arg_reduce(x, "max", dim, keepdim, None, None, False, True, "argmax")[1]
+
+
+def argmin(x: torch.Tensor, dim: int | None = None, keepdim: bool = False) -> torch.Tensor:
+    """The indices of arg_reduce(x, "min", dim, keepdim) alone (int32; torch.argmin's positions: a NaN beats every
+    number here too); no value is written."""
+    return _arg_reduce(x, "min", dim, keepdim, None, None, False, True, "argmin")[1]
+
+
+def _segment_arg(x: torch.Tensor, offsets: torch.Tensor, op, validate, want_values: bool, want_indices: bool, name: str):
+    _check_arg(x, op, name)
+    xc = x.contiguous()
+    _check_segments(xc, offsets, op, name)
+    if validate:
+        _validate_offsets(offsets, xc.numel())
+    if x.is_cuda:
+        v, i = ops().segment_arg_reduce(xc, offsets, OP_CODES[op], want_values, want_indices, None, None)
+    else:
+        v, i = _host_segment_arg(xc.reshape(-1), offsets, op)
+    return (v if want_values else None), (i if want_indices else None)
+
+
+def segment_arg_reduce(x: torch.Tensor, offsets: torch.Tensor, op: str, validate: bool = False):
+    """(values, indices), both [S]: the extremum (op "max" or "min", the rule of arg_reduce: NaN beats every number,
+    -0.0 == +0.0, the lowest position wins ties, the value bit for bit) of every segment x.flatten()[offsets[j] :
+    offsets[j+1]], S = offsets.numel() - 1. indices are int32 FLAT positions in x.flatten() (the convention of
+    segment_sort: offsets[j] <= indices[j] < offsets[j+1]); an empty segment gives -1 and the identity as its value
+    (-inf / INT32_MIN for max, +inf / INT32_MAX for min, as segment_reduce). offsets as for segment_reduce: int32, 1-D,
+    contiguous, on x's device, 0 <= offsets[0] <= ... <= offsets[S] <= x.numel(), not checked unless validate=True (one
+    host sync; ValueError naming the first offending entry); offsets that break it give an unspecified result and
+    touch nothing outside the tensors. Any view of x is accepted; x is never written. Does not synchronise."""
+    return _segment_arg(x, offsets, op, validate, True, True, "segment_arg_reduce")
+
+
+def segment_argmax(x: torch.Tensor, offsets: torch.Tensor, validate: bool = False) -> torch.Tensor:
+    """The indices of segment_arg_reduce(x, offsets, "max") alone; no value is written."""
+    return _segment_arg(x, offsets, "max", validate, False, True, "segment_argmax")[1]
+
+
+def segment_argmin(x: torch.Tensor, offsets: torch.Tensor, validate: bool = False) -> torch.Tensor:
+    """The indices of segment_arg_reduce(x, offsets, "min") alone; no value is written."""
+    return _segment_arg(x, offsets, "min", validate, False, True, "segment_argmin")[1]
