@@ -356,6 +356,35 @@ long long pcmx_searchsorted_workspace_bytes(long long n, long long m, int needle
 int pcmx_searchsorted_b32(const void* sorted_keys, long long n, const void* needles, long long m, int32_t* out,
                           int key_type, int right, int descending, int needles_sorted, void* workspace, hipStream_t s);
 
+/* ---------------------------------------------------------------- set operations on sorted sequences */
+/* Intersection, union, difference and symmetric difference of two SORTED sequences of 32-bit keys, with the multiset
+ * rule of std::set_* (csrc/kernels/setops.hip). Order, key transform, the sortedness precondition (not checked:
+ * unspecified result, but every load and store inside the given buffers) and the modes are pcmx_merge_b32's. Keys are
+ * equal when their transformed keys are. For a key that occurs m times in a and n times in b, the i-th occurrence in
+ * a is paired with the i-th in b, i < min(m, n):
+ *   PCMX_SET_INTERSECTION  keeps the paired elements of a                           capacity min(na, nb)
+ *   PCMX_SET_UNION         keeps all of a and the unpaired elements of b            capacity na + nb
+ *   PCMX_SET_DIFFERENCE    keeps the unpaired elements of a                         capacity na
+ *   PCMX_SET_SYMDIFF       keeps the unpaired elements of both                      capacity na + nb
+ * The output is the kept elements in the order of the merge (a tie goes to a): pcmx_merge_b32's result filtered by
+ * a keep mask, keys moved as raw bits, values (PCMX_MERGE_PAIRS) and indices into the concatenation
+ * (PCMX_MERGE_INDEX, keys_out may be NULL) travelling with their element. *count_out (int64 in device memory, 8-B
+ * aligned) receives the number of kept elements; the outputs have room for the op's capacity and nothing at or past
+ * the count is written. Two launches on the stream behind a hipMemsetAsync of the workspace's head: a partition
+ * kernel (the tile borders and the run counts that cross them) and one block per tile that merges, decides, and
+ * stores compacted at an exact position from the decoupled look-back of the scan (bounded spins; a look-back that
+ * gives up sets the workspace's timeout word, which pcmx_scan_check reads, and ORs 1 into *err_flag, which may be
+ * NULL). Inputs 4-B aligned and never written; outputs and the workspace (pcmx_set_op_workspace_bytes, one call in
+ * flight per workspace) 16-B aligned; no output may overlap an input; na + nb < 2^31. A bad key type, op, mode,
+ * alignment or size, a missing pointer or a workspace_bytes below pcmx_set_op_workspace_bytes returns PCMX_ERR_ARG
+ * and launches nothing. A capacity of 0 writes *count_out = 0 and nothing else. */
+enum { PCMX_SET_INTERSECTION = 0, PCMX_SET_UNION = 1, PCMX_SET_DIFFERENCE = 2, PCMX_SET_SYMDIFF = 3 };
+long long pcmx_set_op_workspace_bytes(long long na, long long nb);
+int pcmx_set_op_b32(const void* keys_a, const void* vals_a, long long na, const void* keys_b, const void* vals_b,
+                    long long nb, void* keys_out, void* vals_or_idx_out, long long* count_out, int op, int mode,
+                    int key_type, int descending, void* workspace, long long workspace_bytes, unsigned* err_flag,
+                    hipStream_t s);
+
 /* ---------------------------------------------------------------- reduction over ragged segments (offsets) */
 /* out[j] = op over x[offsets[j], offsets[j+1]) for j < S: the segments of a CSR row_ptr, torch.segment_reduce with
  * offsets= (csrc/kernels/ragged.hip). offsets holds S + 1 int32 values in device memory with the PRECONDITION

@@ -938,6 +938,91 @@ at::Tensor searchsorted(const at::Tensor& sorted, const at::Tensor& values, bool
     return has_out ? merge_finish(out, dest) : dest.view(values.sizes());
 }
 
+// ---------------------------------------------------------------- set operations on sorted sequences
+// Intersection / union / difference / symmetric difference of two sorted float32 / int32 key sequences, flattened
+// (csrc/kernels/setops.hip). Inputs as for the merge (read where they lie; a non-contiguous one is gathered first).
+// The outputs follow the select ops: they have room for the op's capacity, only [0, count) is written, count is a
+// 0-d int64 tensor on the device and nothing synchronises; a caller's buffer that is not 16-B aligned is written
+// through a copy of itself, so what lies past the count survives. The look-back shares the scan's per-(device, stream)
+// sticky error word, so scan_check() covers these ops.
+int64_t set_capacity(int64_t op, int64_t na, int64_t nb, const char* what) {
+    TORCH_CHECK(op >= PCMX_SET_INTERSECTION && op <= PCMX_SET_SYMDIFF, what, ": unknown op code ", op);
+    return op == PCMX_SET_INTERSECTION ? std::min(na, nb) : (op == PCMX_SET_DIFFERENCE ? na : na + nb);
+}
+
+at::Tensor set_finish(const c10::optional<at::Tensor>& out, const at::Tensor& dest) {
+    if (!(out.has_value() && out->defined())) return dest;
+    if (!dest.is_same(*out)) out->copy_(dest);
+    return *out;
+}
+
+// keys_out / aux_out: destinations or undefined tensors (no such output in this mode); returns the count
+at::Tensor set_launch(const at::Tensor& a, const at::Tensor& b, const at::Tensor* va, const at::Tensor* vb,
+                      at::Tensor keys_out, at::Tensor aux_out, int64_t op, int mode, bool descending, const char* what) {
+    const int key_type = sort_key_type(a, what);
+    hipStream_t stream = cur_stream(a);
+    unsigned* err_dev = scan_err_word(a.device().index(), stream).dev;
+    raise_pending_scan_error(a.device().index(), stream);
+    const int64_t na = a.numel(), nb = b.numel();
+    at::Tensor ac = a, bc = b, vac, vbc;
+    for (const at::Tensor* o : {&keys_out, &aux_out}) {
+        if (!o->defined()) continue;
+        if (overlaps(ac, *o)) ac = ac.clone();
+        if (overlaps(bc, *o)) bc = bc.clone();
+    }
+    if (va) {
+        vac = *va, vbc = *vb;
+        for (const at::Tensor* o : {&keys_out, &aux_out}) {
+            if (overlaps(vac, *o)) vac = vac.clone();
+            if (overlaps(vbc, *o)) vbc = vbc.clone();
+        }
+    }
+    at::Tensor count = at::empty({}, a.options().dtype(at::kLong));
+    auto ws = workspace(a, pcmx_set_op_workspace_bytes(na, nb));
+    check_rc(pcmx_set_op_b32(ac.data_ptr(), va ? vac.data_ptr() : nullptr, na, bc.data_ptr(), va ? vbc.data_ptr() : nullptr,
+                             nb, keys_out.defined() ? keys_out.data_ptr() : nullptr,
+                             aux_out.defined() ? aux_out.data_ptr() : nullptr, (long long*)count.data_ptr<int64_t>(),
+                             (int)op, mode, key_type, descending ? 1 : 0, ws.data_ptr(), ws.numel(), err_dev, stream),
+             what);
+    return count;
+}
+
+// (kept keys, int32 indices into cat(a, b) or an empty tensor, count)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> set_op(const at::Tensor& a, const at::Tensor& b, int64_t op, bool descending,
+                                                      bool want_idx, const c10::optional<at::Tensor>& out_keys,
+                                                      const c10::optional<at::Tensor>& out_idx) {
+    sort_key_type(a, "set_op");
+    const at::DeviceGuard g(a.device());
+    at::Tensor ac = a.contiguous().view(-1), bc = merge_input(b, a, "set_op", "b");
+    merge_total(a, b, "set_op");
+    const int64_t cap = set_capacity(op, ac.numel(), bc.numel(), "set_op");
+    at::Tensor kd = select_dest(out_keys, a, a.scalar_type(), cap, "set_op");
+    at::Tensor id = want_idx ? select_dest(out_idx, a, at::kInt, cap, "set_op") : at::Tensor();
+    at::Tensor count = set_launch(ac, bc, nullptr, nullptr, kd, id, op, want_idx ? PCMX_MERGE_INDEX : PCMX_MERGE_KEYS,
+                                  descending, "set_op");
+    return {set_finish(out_keys, kd), want_idx ? set_finish(out_idx, id) : at::empty({0}, a.options().dtype(at::kInt)),
+            count};
+}
+
+// (kept keys, their values, count)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> set_op_pairs(const at::Tensor& ka, const at::Tensor& va, const at::Tensor& kb,
+                                                            const at::Tensor& vb, int64_t op, bool descending) {
+    sort_key_type(ka, "set_op_pairs");
+    TORCH_CHECK(va.scalar_type() == at::kFloat || va.scalar_type() == at::kInt, "set_op_pairs: values have dtype ",
+                va.scalar_type(), ", expected float32 or int32");
+    TORCH_CHECK(va.numel() == ka.numel() && vb.numel() == kb.numel(), "set_op_pairs: ", va.numel(), " / ", vb.numel(),
+                " values for ", ka.numel(), " / ", kb.numel(), " keys");
+    const at::DeviceGuard g(ka.device());
+    at::Tensor kac = ka.contiguous().view(-1), kbc = merge_input(kb, ka, "set_op_pairs", "keys_b");
+    TORCH_CHECK(va.device() == ka.device(), "set_op_pairs: values_a must be on ", ka.device());
+    at::Tensor vac = va.contiguous().view(-1), vbc = merge_input(vb, va, "set_op_pairs", "values_b");
+    merge_total(ka, kb, "set_op_pairs");
+    const int64_t cap = set_capacity(op, kac.numel(), kbc.numel(), "set_op_pairs");
+    at::Tensor kd = at::empty({cap}, ka.options()), vd = at::empty({cap}, va.options());
+    at::Tensor count = set_launch(kac, kbc, &vac, &vbc, kd, vd, op, PCMX_MERGE_PAIRS, descending, "set_op_pairs");
+    return {kd, vd, count};
+}
+
 // ---------------------------------------------------------------- reduction over ragged segments (offsets)
 // out[j] = op over x.flatten()[offsets[j] : offsets[j+1]] (csrc/kernels/ragged.hip). x and offsets are read where they
 // lie (element alignment is enough). `out` (1-D, contiguous, at least S elements, x's dtype) is returned as out[:S]
@@ -1695,6 +1780,8 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("merge_keys(Tensor a, Tensor b, bool descending=False, Tensor(a!)? out=None) -> Tensor");
     m.def("merge_index(Tensor a, Tensor b, bool descending=False, bool want_keys=True, Tensor(a!)? out_keys=None, Tensor(b!)? out_idx=None) -> (Tensor, Tensor)");
     m.def("merge_pairs(Tensor keys_a, Tensor values_a, Tensor keys_b, Tensor values_b, bool descending=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_values=None) -> (Tensor, Tensor)");
+    m.def("set_op(Tensor a, Tensor b, int op, bool descending=False, bool want_idx=False, Tensor(a!)? out_keys=None, Tensor(b!)? out_idx=None) -> (Tensor, Tensor, Tensor)");
+    m.def("set_op_pairs(Tensor keys_a, Tensor values_a, Tensor keys_b, Tensor values_b, int op, bool descending=False) -> (Tensor, Tensor, Tensor)");
     m.def("searchsorted(Tensor sorted_sequence, Tensor values, bool right=False, bool descending=False, bool values_sorted=False, Tensor(a!)? out=None) -> Tensor");
     m.def("segment_reduce(Tensor x, Tensor offsets, int op, Tensor(a!)? out=None) -> Tensor");
     m.def("segment_heads(Tensor offsets, int n, Tensor like) -> Tensor");
@@ -1764,6 +1851,8 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("merge_keys", merge_keys);
     m.impl("merge_index", merge_index);
     m.impl("merge_pairs", merge_pairs);
+    m.impl("set_op", set_op);
+    m.impl("set_op_pairs", set_op_pairs);
     m.impl("searchsorted", searchsorted);
     m.impl("segment_reduce", segment_reduce);
     m.impl("segment_heads", segment_heads);

@@ -10,7 +10,7 @@ import torch
 
 from .. import ops
 from ..ops.sparse import powerlaw_row_ptr
-from ..ops.vector import _axis_plan
+from ..ops.vector import SET_OP_CODES, _axis_plan
 from ..parallel.collectives import global_scan
 from ..parallel.dist import Context
 
@@ -1705,11 +1705,117 @@ class ArgReduce(Workload):
         return rep
 
 
+class SetOps(Workload):
+    """A set operation on two sorted key arrays of n keys per GPU in all (csrc/kernels/setops.hip): op intersection,
+    union, difference or symmetric_difference; mode "keys" (ops.set_compact), "index" (keys and int32 indices into the
+    concatenation) or "pairs" (ops.set_compact_by_key with an int32 payload). split is the fraction of n that is a.
+    dtype f32 (uniform in [-1, 1)) or i32 (full range). dist: "interleaved" (both sides drawn from the same range),
+    "disjoint" (every key of a below every key of b), "identical" (both sides are prefixes of one sorted array: equal
+    sides at split 0.5), "ties" (eight distinct keys) or "equal" (one key everywhere). The timed step does not
+    synchronise: the count stays on the device. No communication (weak scaling)."""
+
+    MODES = ("keys", "index", "pairs")
+    DISTS = ("interleaved", "disjoint", "identical", "ties", "equal")
+
+    def __init__(self, ctx, n=1 << 28, op="intersection", mode="keys", dtype="f32", dist="interleaved", split=0.5,
+                 descending=False, **_):
+        if op not in SET_OP_CODES:
+            raise ValueError(f"setops op {op!r}: one of {', '.join(SET_OP_CODES)}")
+        if mode not in self.MODES:
+            raise ValueError(f"setops mode {mode!r}: one of {', '.join(self.MODES)}")
+        if dtype not in ("f32", "i32"):
+            raise ValueError(f"setops dtype {dtype!r}: f32 or i32")
+        if dist not in self.DISTS:
+            raise ValueError(f"setops dist {dist!r}: one of {', '.join(self.DISTS)}")
+        if not 0.0 <= float(split) <= 1.0:
+            raise ValueError(f"setops split {split!r}: a fraction in [0, 1]")
+        na = int(round(int(n) * float(split)))
+        nb, dev = int(n) - na, ctx.device
+        super().__init__(ctx, {"n": na + nb, "na": na, "nb": nb, "op": op, "mode": mode, "dtype": dtype, "dist": dist,
+                               "descending": bool(descending)}, "setops", "GB/s")
+        self.op, self.mode, self.descending = op, mode, bool(descending)
+
+        def keys(count, seed, half):
+            """count sorted keys; half -1 / +1: from the lower / upper half of the range (dist disjoint), 0: all of it"""
+            g = torch.Generator(device=dev).manual_seed(seed)
+            if dist == "ties":
+                x = torch.randint(0, 8, (count,), device=dev, generator=g).to(torch.float32 if dtype == "f32" else torch.int32)
+            elif dtype == "f32":
+                lo, hi = (-1.0, 1.0) if half == 0 else ((-1.0, 0.0) if half < 0 else (0.0, 1.0))
+                x = ops.rand_uniform_(torch.empty(count, device=dev), seed, lo, hi)
+            else:
+                lo, hi = (-(1 << 31), 1 << 31) if half == 0 else ((-(1 << 31), 0) if half < 0 else (0, 1 << 31))
+                x = torch.randint(lo, hi, (count,), device=dev, generator=g, dtype=torch.int64).to(torch.int32)
+            if dist == "equal":
+                x.fill_(0.5 if dtype == "f32" else 1)
+            return torch.sort(x, descending=self.descending).values
+
+        if dist == "identical":
+            both = keys(max(na, nb), 17000 + ctx.rank, 0)
+            self.a, self.b = both[:na].clone(), both[:nb].clone()
+        else:
+            first = (-1 if dist == "disjoint" else 0) * (-1 if self.descending else 1)
+            self.a, self.b = keys(na, 17000 + ctx.rank, first), keys(nb, 18000 + ctx.rank, -first)
+        self.va = torch.arange(na, device=dev, dtype=torch.int32) if mode == "pairs" else None
+        self.vb = torch.arange(na, na + nb, device=dev, dtype=torch.int32) if mode == "pairs" else None
+        self.out = None
+
+    def step(self):
+        if self.mode == "pairs":
+            self.out = ops.set_compact_by_key(self.a, self.va, self.b, self.vb, self.op, self.descending)
+        else:
+            self.out = ops.set_compact(self.a, self.b, self.op, self.descending, indices=self.mode == "index")
+
+    def reference(self) -> torch.Tensor:
+        """int64 positions in cat(a, b) of the kept elements in merge order, from the stable torch.sort of the
+        concatenation and its runs of equal keys (the generated keys hold no NaN): inside a run come the m elements
+        of a, then the n of b, and the i-th of each side are partners."""
+        cat = torch.cat([self.a, self.b])
+        na = self.a.numel()
+        r = torch.sort(cat, stable=True, descending=self.descending)
+        _, run, length = torch.unique_consecutive(r.values, return_inverse=True, return_counts=True)
+        from_a = r.indices < na
+        m = torch.zeros_like(length).scatter_add_(0, run, from_a.long())
+        start = torch.cumsum(length, 0) - length
+        place = torch.arange(cat.numel(), device=cat.device) - start[run]  # place in the run
+        paired = torch.where(from_a, place < (length - m)[run], place - m[run] < m[run])
+        keep = {"intersection": from_a & paired, "union": from_a | ~paired, "difference": from_a & ~paired,
+                "symmetric_difference": ~paired}[self.op]
+        return r.indices[keep]
+
+    def work_per_step(self):
+        # bytes moved: both inputs are read once (4 more per key for a payload), every kept element is written once
+        # (4 more for its value or index). The kept count is that of the last step (one sync, after the timed window).
+        n = self.a.numel() + self.b.numel()
+        kept = int(self.out[-1].item()) if self.out is not None else 0
+        return float(n * (8 if self.mode == "pairs" else 4) + kept * (4 if self.mode == "keys" else 8))
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["gkeys_per_s"] = self.ctx.world * (self.a.numel() + self.b.numel()) * steps / seconds / 1e9
+        rep["kept"] = int(self.out[-1].item())
+        return rep
+
+    def check(self, reduce: bool = True):
+        """The outputs of the timed step against reference(), exactly: the count, the kept keys bit for bit, and the
+        indices or the payload (which names every element's place in the concatenation). Local only."""
+        ref = self.reference()
+        k = int(self.out[-1].item())
+        cat = torch.cat([self.a, self.b]).view(torch.int32)
+        ok = k == ref.numel() and torch.equal(self.out[0][:k].view(torch.int32), cat[ref])
+        if ok and self.mode != "keys":
+            ok = self.out[1].dtype == torch.int32 and torch.equal(self.out[1][:k], ref.int())
+        ok = bool(ok)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"elements_checked": self.a.numel() + self.b.numel(), "kept": k, "exact_vs_torch": ok, "check_passed": ok}
+
+
 WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
              "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
              "merge": Merge, "rowsort": RowSort, "axis": Axis, "ragged": Ragged, "segsort": SegSort,
-             "argreduce": ArgReduce}
+             "argreduce": ArgReduce, "setops": SetOps}
 
 
 def build_workload(name: str, ctx: Context, **cfg) -> Workload:

@@ -19,6 +19,10 @@ from .vector import segment_argsort, segment_sort, segment_sort_by_key, segment_
 # arg_reduce / argmax / argmin (flat or dim=int) and segment_arg_reduce / segment_argmax / segment_argmin say where the
 # extremum is (csrc/kernels/argreduce.hip; ARG_BLOCK, ARG_MAX_BLOCKS)
 from .vector import arg_reduce, argmax, argmin, segment_arg_reduce, segment_argmax, segment_argmin
+# set operations on SORTED tensors (multiset rule of std::set_*, csrc/kernels/setops.hip; SETOP_TILE, SET_OP_CODES) and
+# their numpy-style forms for unsorted input
+from .vector import (intersect1d, set_compact, set_compact_by_key, set_difference, set_intersection, set_op_by_key,
+                     set_symmetric_difference, set_union, setdiff1d, setxor1d, union1d)
 
 __all__ = [
     "sgemm", "sgemm_out", "sgemm_simt", "sgemm_naive_host",
@@ -37,4 +41,6 @@ __all__ = [
     "segment_reduce", "segment_scan",
     "segment_sort_keys", "segment_sort", "segment_argsort", "segment_sort_by_key",
     "arg_reduce", "argmax", "argmin", "segment_arg_reduce", "segment_argmax", "segment_argmin",
+    "set_compact", "set_compact_by_key", "set_intersection", "set_union", "set_difference", "set_symmetric_difference",
+    "set_op_by_key", "intersect1d", "union1d", "setdiff1d", "setxor1d",
 ]

@@ -1375,6 +1375,20 @@ def _check_merge(a: torch.Tensor, b: torch.Tensor, name: str) -> None:
         raise ValueError(f"{name}: {a.numel()} + {b.numel()} elements; indices are int32 (at most 2^31 - 1 together)")
 
 
+def _check_merge_pairs(keys_a, values_a, keys_b, values_b, name: str) -> None:
+    _check_merge_keys(keys_a, keys_b, name, "keys_a", "keys_b")
+    if values_a.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name}: values must be float32 or int32, got {values_a.dtype}")
+    if values_b.dtype != values_a.dtype:
+        raise TypeError(f"{name}: values_b is {values_b.dtype}, values_a is {values_a.dtype}")
+    for k, v, side in ((keys_a, values_a, "a"), (keys_b, values_b, "b")):
+        if v.numel() != k.numel():
+            raise ValueError(f"{name}: {v.numel()} values for {k.numel()} keys on side {side}")
+        if v.device != keys_a.device:
+            raise ValueError(f"{name}: values_{side} are on {v.device}, the keys on {keys_a.device}")
+    _check_merge(keys_a, keys_b, name)
+
+
 def _order_key64(x: torch.Tensor, descending: bool) -> torch.Tensor:
     """int64 keys of flat x whose ascending order is the wanted order: radix_key.h's to_key, computed with torch."""
     b = x.reshape(-1).contiguous().view(torch.int32).long() & 0xFFFFFFFF
@@ -1419,17 +1433,7 @@ def merge_by_key(keys_a: torch.Tensor, values_a: torch.Tensor, keys_b: torch.Ten
                  descending: bool = False):
     """(keys, values): the merge of two sorted key tensors with their values (float32 or int32, the same dtype on both
     sides, one per key, moved as bits) carried along. A tie goes to a."""
-    _check_merge_keys(keys_a, keys_b, "merge_by_key", "keys_a", "keys_b")
-    if values_a.dtype not in (torch.float32, torch.int32):
-        raise TypeError(f"merge_by_key: values must be float32 or int32, got {values_a.dtype}")
-    if values_b.dtype != values_a.dtype:
-        raise TypeError(f"merge_by_key: values_b is {values_b.dtype}, values_a is {values_a.dtype}")
-    for k, v, side in ((keys_a, values_a, "a"), (keys_b, values_b, "b")):
-        if v.numel() != k.numel():
-            raise ValueError(f"merge_by_key: {v.numel()} values for {k.numel()} keys on side {side}")
-        if v.device != keys_a.device:
-            raise ValueError(f"merge_by_key: values_{side} are on {v.device}, the keys on {keys_a.device}")
-    _check_merge(keys_a, keys_b, "merge_by_key")
+    _check_merge_pairs(keys_a, values_a, keys_b, values_b, "merge_by_key")
     if keys_a.is_cuda:
         return tuple(ops().merge_pairs(keys_a, values_a, keys_b, values_b, bool(descending), None, None))
     bits, order = _host_merge(keys_a, keys_b, bool(descending))
@@ -1476,6 +1480,149 @@ def searchsorted(sorted_sequence: torch.Tensor, values: torch.Tensor, right: boo
 def bucketize(values: torch.Tensor, boundaries: torch.Tensor, right: bool = False) -> torch.Tensor:
     """torch.bucketize with int32 results: searchsorted(boundaries, values, right) for ascending boundaries."""
     return searchsorted(boundaries, values, right=right)
+
+
+# ---------------------------------------------------------------- set operations on sorted sequences
+# Intersection, union, difference and symmetric difference of two SORTED tensors (thrust::set_*, std::set_*): what one
+# does with sorted id lists. float32 or int32, same dtype and device, flattened, sorted in the merge's order (above;
+# descending=True for descending input); sortedness is the caller's duty and is not checked (unsorted input gives an
+# unspecified result, but nothing outside the tensors is touched); a.numel() + b.numel() < 2^31. On the GPU one fused
+# pass on the merge-path tiles (csrc/kernels/setops.hip; no counterpart in the reference programs): a partition kernel,
+# then one block per SETOP_TILE merged positions that merges in LDS, decides per element, and stores compacted at an
+# exact position from the decoupled look-back (scan_check() reports a look-back that gave up, as for select).
+#  * Two elements are EQUAL when their transformed keys are: -0.0 == +0.0, every NaN equals every NaN.
+#  * MULTISETS, by position. For a key that occurs m times in a and n times in b, the i-th occurrence in a is paired
+#    with the i-th in b for i < min(m, n). Then
+#        intersection          keeps the paired elements of a (the first min(m, n))         capacity min(na, nb)
+#        difference            keeps the unpaired elements of a (the last max(m - n, 0))    capacity na
+#        union                 keeps all of a and the unpaired elements of b (the last max(n - m, 0))   na + nb
+#        symmetric_difference  keeps the unpaired elements of both                          capacity na + nb
+#  * The result is the kept elements IN THE ORDER OF merge(a, b) (a tie goes to a): the merge filtered by a keep mask.
+#    Keys are moved as their raw bits and nothing is transformed: the intersection of [-0.0] and [+0.0] is [-0.0], and
+#    NaN payloads survive. Indices, where asked for, are int32 positions in cat(a.flatten(), b.flatten()), as in merge;
+#    in the by-key forms a value travels with its kept element.
+#  * set_compact / set_compact_by_key follow compact: the outputs have the op's capacity, only [:count] is written,
+#    count is a 0-d int64 tensor on the inputs' device, nothing synchronises. set_intersection / set_union /
+#    set_difference / set_symmetric_difference / set_op_by_key cut to the exact size (one host sync for the count).
+#    intersect1d / union1d / setdiff1d / setxor1d are numpy's: unsorted input of any shape, unique() on each side (so
+#    both zeros are +0.0 and all NaNs are one canonical NaN, last), then the set op.
+#  * An input that is not contiguous is gathered first; a slice such as x[1:] is read where it lies.
+SETOP_TILE = 4352          # csrc/kernels/setops.hip kTile: merged positions per block (the merge's tile)
+SET_OP_CODES = {"intersection": 0, "union": 1, "difference": 2, "symmetric_difference": 3}   # PCMX_SET_*
+
+
+def _set_capacity(op: str, na: int, nb: int, name: str) -> int:
+    if op not in SET_OP_CODES:
+        raise ValueError(f"{name}: op must be one of {sorted(SET_OP_CODES)}, got {op!r}")
+    return min(na, nb) if op == "intersection" else (na if op == "difference" else na + nb)
+
+
+def _host_set(a: torch.Tensor, b: torch.Tensor, op: str, descending: bool):
+    """(int32 view of the concatenation, int64 positions in it of the kept elements, in merge order): the definition
+    above with torch ops."""
+    af, bf = a.reshape(-1), b.reshape(-1)
+    ka, kb = _order_key64(af, descending), _order_key64(bf, descending)
+
+    def paired(own, other):  # rank in the element's own run < length of the other side's run of its key
+        lower = torch.searchsorted(own, own)
+        upper = torch.searchsorted(other, own, right=True)
+        return torch.arange(own.numel(), device=own.device) - lower < upper - torch.searchsorted(other, own)
+
+    pa, pb = paired(ka, kb), paired(kb, ka)
+    keep = {"intersection": (pa, torch.zeros_like(pb)), "union": (torch.ones_like(pa), ~pb),
+            "difference": (~pa, torch.zeros_like(pb)), "symmetric_difference": (~pa, ~pb)}[op]
+    order = torch.sort(torch.cat([ka, kb]), stable=True).indices  # a tie goes to a
+    return torch.cat([af, bf]).view(torch.int32), order[torch.cat(keep)[order]]
+
+
+def set_compact(a: torch.Tensor, b: torch.Tensor, op: str, descending: bool = False, indices: bool = False,
+                out_keys: torch.Tensor | None = None, out_indices: torch.Tensor | None = None):
+    """(keys, count), or (keys, idx, count) with indices=True: the set operation `op` (a key of SET_OP_CODES) on two
+    sorted tensors, rules above. keys (a's dtype) and idx (int32 positions in cat(a.flatten(), b.flatten())) have the
+    op's capacity and are written in [:count] only; count is a 0-d int64 tensor on a's device. out_keys / out_indices
+    (optional, 1-D, contiguous, at least the capacity) are left untouched from count on. Does not synchronise."""
+    _check_merge(a, b, "set_compact")
+    cap = _set_capacity(op, a.numel(), b.numel(), "set_compact")
+    if out_indices is not None and not indices:
+        raise ValueError("set_compact: out_indices needs indices=True")
+    _check_out(out_keys, a.dtype, cap, a)
+    _check_out(out_indices, torch.int32, cap, a)
+    if a.is_cuda:
+        keys, idx, count = ops().set_op(a, b, SET_OP_CODES[op], bool(descending), bool(indices), out_keys, out_indices)
+        return (keys, idx, count) if indices else (keys, count)
+    bits, kept = _host_set(a, b, op, bool(descending))
+    keys, count = _host_result(bits[kept].view(a.dtype), cap, out_keys)
+    return (keys, _host_result(kept.int(), cap, out_indices)[0], count) if indices else (keys, count)
+
+
+def set_compact_by_key(keys_a: torch.Tensor, values_a: torch.Tensor, keys_b: torch.Tensor, values_b: torch.Tensor,
+                       op: str, descending: bool = False):
+    """(keys, values, count): set_compact with a value per key (float32 or int32, the same dtype on both sides, moved
+    as bits) that travels with its kept element. Does not synchronise."""
+    _check_merge_pairs(keys_a, values_a, keys_b, values_b, "set_compact_by_key")
+    cap = _set_capacity(op, keys_a.numel(), keys_b.numel(), "set_compact_by_key")
+    if keys_a.is_cuda:
+        return tuple(ops().set_op_pairs(keys_a, values_a, keys_b, values_b, SET_OP_CODES[op], bool(descending)))
+    bits, kept = _host_set(keys_a, keys_b, op, bool(descending))
+    # (indexing an int32 view: a float gather would be free to quieten a signalling NaN payload)
+    vbits = torch.cat([values_a.reshape(-1), values_b.reshape(-1)]).view(torch.int32)[kept]
+    keys, count = _host_result(bits[kept].view(keys_a.dtype), cap, None)
+    return keys, _host_result(vbits.view(values_a.dtype), cap, None)[0], count
+
+
+def _set_exact(a, b, op: str, descending: bool, return_indices: bool):
+    r = set_compact(a, b, op, descending, indices=return_indices)
+    k = int(r[-1].item())
+    return (r[0][:k], r[1][:k]) if return_indices else r[0][:k]
+
+
+def set_intersection(a: torch.Tensor, b: torch.Tensor, descending: bool = False, return_indices: bool = False):
+    """The elements of sorted a that have a partner in sorted b (multiset rule above), at exact size (one host sync);
+    with return_indices (keys, int32 positions in cat(a.flatten(), b.flatten()))."""
+    return _set_exact(a, b, "intersection", descending, return_indices)
+
+
+def set_union(a: torch.Tensor, b: torch.Tensor, descending: bool = False, return_indices: bool = False):
+    """All of sorted a and the elements of sorted b without a partner in a, in merge order, at exact size."""
+    return _set_exact(a, b, "union", descending, return_indices)
+
+
+def set_difference(a: torch.Tensor, b: torch.Tensor, descending: bool = False, return_indices: bool = False):
+    """The elements of sorted a without a partner in sorted b, at exact size."""
+    return _set_exact(a, b, "difference", descending, return_indices)
+
+
+def set_symmetric_difference(a: torch.Tensor, b: torch.Tensor, descending: bool = False, return_indices: bool = False):
+    """The elements of either sorted tensor without a partner in the other, in merge order, at exact size."""
+    return _set_exact(a, b, "symmetric_difference", descending, return_indices)
+
+
+def set_op_by_key(keys_a: torch.Tensor, values_a: torch.Tensor, keys_b: torch.Tensor, values_b: torch.Tensor, op: str,
+                  descending: bool = False):
+    """(keys, values) of set_compact_by_key at exact size (one host sync for the count)."""
+    keys, values, count = set_compact_by_key(keys_a, values_a, keys_b, values_b, op, descending)
+    k = int(count.item())
+    return keys[:k], values[:k]
+
+
+def intersect1d(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """np.intersect1d: the sorted distinct values present in both x and y (any shape, any order)."""
+    return set_intersection(unique(x), unique(y))
+
+
+def union1d(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """np.union1d: the sorted distinct values present in x or in y."""
+    return set_union(unique(x), unique(y))
+
+
+def setdiff1d(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """np.setdiff1d: the sorted distinct values of x that are not in y."""
+    return set_difference(unique(x), unique(y))
+
+
+def setxor1d(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """np.setxor1d: the sorted distinct values present in exactly one of x and y."""
+    return set_symmetric_difference(unique(x), unique(y))
 
 
 # ---------------------------------------------------------------- reduction / scan over ragged segments (offsets)
