@@ -272,6 +272,22 @@ PCMX_SCALAR_GATHER void pcmx_spmv_csr_omp(int n_rows, const int* row_ptr, const 
     }
 }
 
+/* Y[n_rows, k] = A X, X and Y row-major with leading dimensions ldx, ldy >= k: rows in parallel, a row's nonzeros
+ * in order, the inner loop over the k columns (columns k .. ldy - 1 of Y are not touched). */
+void pcmx_spmm_csr_omp(int n_rows, const long long* row_ptr, const int* col_ind, const float* values, const float* x,
+                       long long ldx, float* y, long long ldy, int k) {
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int i = 0; i < n_rows; ++i) {
+        float* yi = y + (long long)i * ldy;
+        for (int c = 0; c < k; ++c) yi[c] = 0.0f;
+        for (long long p = row_ptr[i]; p < row_ptr[i + 1]; ++p) {
+            const float* xr = x + (long long)col_ind[p] * ldx;
+            const float v = values[p];
+            for (int c = 0; c < k; ++c) yi[c] += v * xr[c];
+        }
+    }
+}
+
 /* ---------------------------------------------------------------- power-law generator */
 
 static inline unsigned long long splitmix64(unsigned long long* s) {

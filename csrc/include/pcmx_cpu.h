@@ -94,6 +94,9 @@ void multiply(s_matrix_t* matrix, float* v, float* r);
 /* multithreaded variants */
 void pcmx_spmv_csr_omp(int n_rows, const int* row_ptr, const int* col_ind, const float* values,
                        const float* v, float* r);
+/* Y[n_rows, k] = A X (row-major X, Y with leading dimensions ldx, ldy >= k; int64 row_ptr): OpenMP over rows */
+void pcmx_spmm_csr_omp(int n_rows, const long long* row_ptr, const int* col_ind, const float* values, const float* x,
+                       long long ldx, float* y, long long ldy, int k);
 void pcmx_spmv_banded_omp(const s_matrix_t* matrix, const float* v, float* r);
 /* band limits of row i: 5 half-open column ranges [lo[k], hi[k]) (the row's nnz in order). */
 void pcmx_band_ranges(int n, int a, int b, int c, int d, int e, int row, int lo[5], int hi[5]);

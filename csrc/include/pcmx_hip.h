@@ -660,6 +660,30 @@ int pcmx_spmv_banded_variant(const float* vals, const long long* row_off, int n,
  * with n <= 0 launches nothing. */
 int pcmx_spmv_banded_path(int n, int a, int b, int c, int d, int e, int variant, int vals_aligned, int* nl);
 
+/* ---------------------------------------------------------------- SpMM (kernels/spmm.hip) */
+/* Y[n_rows, k] = A X for a CSR matrix and row-major f32 X (leading dimension ldx >= k) and Y (ldy >= k); device
+ * arrays. items / n_items: the work items of pcmx_spmv_csr_plan_nnz(item_nnz). slot[item]: the workspace slot of a
+ * piece of a split row (the pieces of one row take consecutive slots in piece order), -1 for every other item.
+ * split: n_split x {row, first slot, pieces} (int32). ws: n_pieces rows of ((k + 3) & ~3) floats, 16-B aligned;
+ * ws_floats its size. One wave per item and column tile; a fix-up launch sums each split row's pieces in piece order:
+ * no atomics, no memset, the same bits on every call. Every row of Y is written once (an empty row as +0.0), columns
+ * k .. ldy - 1 are not touched. Returns PCMX_ERR_ARG, before anything is launched, for k < 0, n_rows < 0, ldx < k,
+ * ldy < k, an item_nnz that is no multiple of 64 in 64..1024, a workspace smaller than n_pieces rows (or misaligned),
+ * and n_rows > 0 without items. */
+int pcmx_spmm_csr(const long long* row_ptr, const int* col, const float* val, const float* x, long long ldx, float* y,
+                  long long ldy, int n_rows, int k, const void* items, long long n_items, const int* slot,
+                  const int* split, int n_split, long long n_pieces, int item_nnz, float* ws, long long ws_floats,
+                  hipStream_t s);
+/* Which kernels pcmx_spmm_csr takes for these operands, from the predicate the launcher dispatches on; launches
+ * nothing and reads no memory (x_addr / y_addr: the operands' addresses). Returns the class of the first column tile:
+ * 4, 8, 16 or 32 lanes per group (k <= 32), or a tile of 64 (from k = 33), 128 or 256 columns (256 for every
+ * k >= 256); 0 for k == 0;
+ * PCMX_ERR_ARG for k < 0, ldx < k or ldy < k. *tail_class (may be NULL): the class of the partial last tile of a
+ * k > 256 (0: none). *vec (may be NULL): bit 0: the first class moves float2 / float4 (both addresses and both leading
+ * dimensions aligned to its vector), bit 1: so does the tail class; a clear bit on a 128 / 256 class means dword form. */
+int pcmx_spmm_path(int k, unsigned long long x_addr, long long ldx, unsigned long long y_addr, long long ldy,
+                   int* tail_class, int* vec);
+
 /* ---------------------------------------------------------------- halo pack/unpack */
 int pcmx_pack_edges(const void* tile, int elem_bytes, int H, int W, int ld, void* buf, hipStream_t s);
 int pcmx_unpack_halo(void* tile, int elem_bytes, int H, int W, int ld, const void* buf, int mask, hipStream_t s);

@@ -1512,6 +1512,40 @@ at::Tensor spmv_csr(const at::Tensor& row_ptr, const at::Tensor& col, const at::
     return y;
 }
 
+// out[n_rows, k] = A x[n_cols, k] (spmm.hip). x and out are 2-D f32 views with unit column stride, read and written
+// where they lie; items / slot / split: the plan of spmm_csr_plan(row_ptr, item_nnz), n_pieces its workspace rows. The
+// workspace comes from torch's allocator on the current stream.
+at::Tensor spmm_csr(const at::Tensor& row_ptr, const at::Tensor& col, const at::Tensor& val, const at::Tensor& x,
+                    const at::Tensor& items, const at::Tensor& slot, const at::Tensor& split, int64_t n_pieces,
+                    int64_t item_nnz, at::Tensor out) {
+    check_gpu(row_ptr, "row_ptr", at::kLong), check_gpu(col, "col", at::kInt), check_gpu(val, "val", at::kFloat);
+    check_gpu(x, "x", at::kFloat), check_gpu(out, "out", at::kFloat), check_gpu(items, "items", at::kLong);
+    check_gpu(slot, "slot", at::kInt), check_gpu(split, "split", at::kInt);
+    const int64_t n_rows = row_ptr.numel() - 1;
+    TORCH_CHECK(x.dim() == 2 && out.dim() == 2 && out.size(0) == n_rows && out.size(1) == x.size(1),
+                "spmm_csr: x [n_cols, k] and out [n_rows, k]");
+    const int64_t k = x.size(1);
+    TORCH_CHECK((k <= 1 || (x.stride(1) == 1 && out.stride(1) == 1)), "spmm_csr: x and out need a unit column stride");
+    TORCH_CHECK(row_ptr.is_contiguous() && col.is_contiguous() && val.is_contiguous() && items.is_contiguous() &&
+                    slot.is_contiguous() && split.is_contiguous() && items.dim() == 2 && items.size(1) == 3 &&
+                    slot.numel() == items.size(0) && (split.numel() == 0 || (split.dim() == 2 && split.size(1) == 3)),
+                "spmm_csr: contiguous CSR arrays and plan (items [n, 3], slot [n], split [s, 3])");
+    TORCH_CHECK(n_pieces >= 0 && n_rows < (1LL << 31) && k < (1LL << 31), "spmm_csr: sizes");
+    const at::DeviceGuard g(val.device());
+    // a dimension of size <= 1 carries an arbitrary stride
+    const int64_t ldx = x.size(0) > 1 ? x.stride(0) : std::max<int64_t>(x.stride(0), k);
+    const int64_t ldy = n_rows > 1 ? out.stride(0) : std::max<int64_t>(out.stride(0), k);
+    const int64_t ws_floats = n_pieces * ((k + 3) & ~int64_t(3));
+    auto ws = at::empty({ws_floats}, val.options());
+    check_rc(pcmx_spmm_csr((const long long*)row_ptr.data_ptr<int64_t>(), col.data_ptr<int>(), val.data_ptr<float>(),
+                           x.data_ptr<float>(), ldx, out.data_ptr<float>(), ldy, (int)n_rows, (int)k, items.data_ptr(),
+                           items.size(0), slot.data_ptr<int>(), split.data_ptr<int>(),
+                           split.numel() ? (int)split.size(0) : 0, n_pieces, (int)item_nnz,
+                           ws_floats ? ws.data_ptr<float>() : nullptr, ws_floats, cur_stream(val)),
+             "spmm_csr");
+    return out;
+}
+
 namespace {
 // the named launch options of the sliced ops, refused here before anything is launched or written
 void check_sliced_options(const char* op, int64_t item_nnz, bool packed, int64_t blocks_per_cu) {
@@ -1741,6 +1775,36 @@ at::Tensor spmv_csr_plan(const at::Tensor& row_ptr, int64_t item_nnz) {
     return items;
 }
 
+// the SpMM plan of a CPU int64 row_ptr: (items [n, 3] int64, slot [n] int32, split [s, 3] int32). A piece of a split
+// row (a one-row item that is not the whole row) takes the next workspace slot, so the pieces of one row hold
+// consecutive slots in piece order; split lists {row, first slot, pieces} per split row; every other item has slot -1.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> spmm_csr_plan(const at::Tensor& row_ptr, int64_t item_nnz) {
+    auto items = spmv_csr_plan(row_ptr, item_nnz);
+    auto rp = row_ptr.contiguous();
+    const int64_t* p = rp.data_ptr<int64_t>();
+    const int64_t n = items.size(0);
+    const int64_t* it = items.data_ptr<int64_t>();
+    auto slot = at::empty({n}, rp.options().dtype(at::kInt));
+    int* sl = slot.data_ptr<int>();
+    std::vector<int> split;
+    int64_t pieces = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t row0 = it[3 * i] & 0xFFFFFFFFLL, row1 = it[3 * i] >> 32;
+        const bool piece = row1 == row0 + 1 && (it[3 * i + 1] != p[row0] || it[3 * i + 2] != p[row0 + 1]);
+        sl[i] = piece ? (int)pieces : -1;
+        if (!piece) continue;
+        TORCH_CHECK(pieces < (1LL << 31) - 1, "spmm_csr_plan: too many pieces");
+        if (it[3 * i + 1] == p[row0])
+            split.insert(split.end(), {(int)row0, (int)pieces, 1});
+        else
+            ++split.back();
+        ++pieces;
+    }
+    auto sp = at::empty({(int64_t)split.size() / 3, 3}, slot.options());
+    std::copy(split.begin(), split.end(), sp.data_ptr<int>());
+    return {items, slot, sp};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(pcmx, m) {
@@ -1807,6 +1871,8 @@ TORCH_LIBRARY(pcmx, m) {
     m.def("stencil5xT_(Tensor u, Tensor(a!) out, int halo, int steps, int r0, int r1, int global_row0, int global_rows, float k, int shape=0) -> ()");
     m.def("stencil5xT_spans_(Tensor u, Tensor(a!) out, int halo, int steps, int r0a, int r1a, int r0b, int r1b, int global_row0, int global_rows, float k, int shape=0) -> ()");
     m.def("spmv_csr(Tensor row_ptr, Tensor col, Tensor val, Tensor x, Tensor items) -> Tensor");
+    m.def("spmm_csr(Tensor row_ptr, Tensor col, Tensor val, Tensor x, Tensor items, Tensor slot, Tensor split, int n_pieces, "
+          "int item_nnz, Tensor(a!) out) -> Tensor(a!)");
     m.def("spmv_sliced(Tensor lrow, Tensor col, Tensor val, Tensor x, Tensor items, Tensor row_mask, Tensor chunk_base, Tensor fix, Tensor meta, Tensor(a!) ypart, Tensor(b!) extra, int n_rows, Tensor(c!)? out=None, bool packed=False, int item_nnz=1024, int stage=0, bool ballot_combine=False, int blocks_per_cu=0, int phase_lo=0, int phase_n=0) -> Tensor");
     m.def("spmv_sliced_pair(Tensor x, int item_nnz, int blocks_per_cu, Tensor col_a, Tensor val_a, Tensor items_a, Tensor meta_a, Tensor(a!) ypart_a, Tensor(b!) extra_a, int s_a, int a_lo, int a_n, Tensor col_b, Tensor val_b, Tensor items_b, Tensor meta_b, Tensor(c!) ypart_b, Tensor(d!) extra_b, int s_b, int b_lo, int b_n) -> ()");
     m.def("spmv_sliced_combine(Tensor ypart, Tensor row_mask, Tensor chunk_base, Tensor meta, int n_slices, Tensor extra, Tensor fix, Tensor? fix_chunk0, Tensor(a!) out, int n_rows, Tensor? send_ptr=None, Tensor? send_slot=None, Tensor(b!)? sendbuf=None) -> ()");
@@ -1877,6 +1943,7 @@ TORCH_LIBRARY_IMPL(pcmx, CUDA, m) {
     m.impl("stencil5xT_", stencil5xT_);
     m.impl("stencil5xT_spans_", stencil5xT_spans_);
     m.impl("spmv_csr", spmv_csr);
+    m.impl("spmm_csr", spmm_csr);
     m.impl("spmv_sliced", spmv_sliced);
     m.impl("spmv_sliced_pair", spmv_sliced_pair);
     m.impl("spmv_sliced_combine", spmv_sliced_combine);
@@ -1930,6 +1997,8 @@ PYBIND11_MODULE(_C, mod) {
     mod.doc() = "pcmx MI355X kernels (ops live under torch.ops.pcmx)";
     mod.def("device_count", []() { return pcmx_device_count(); });
     mod.def("spmv_csr_plan", &spmv_csr_plan, "CSR-adaptive work items from a CPU int64 row_ptr",
+            pybind11::arg("row_ptr"), pybind11::arg("item_nnz") = 1024);
+    mod.def("spmm_csr_plan", &spmm_csr_plan, "SpMM plan from a CPU int64 row_ptr: (items, slot per item, split rows)",
             pybind11::arg("row_ptr"), pybind11::arg("item_nnz") = 1024);
     mod.def("xcomm_unique_id", &xcomm_unique_id, "ncclUniqueId of a new dedicated RCCL communicator (rank 0)");
     mod.def("xcomm_create", &xcomm_create, "join the dedicated RCCL communicator: handle");

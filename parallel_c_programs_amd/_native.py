@@ -116,6 +116,7 @@ def _declare_cpu(lib: ctypes.CDLL) -> ctypes.CDLL:
         "pcmx_create_data_hash": (None, [P, I, ctypes.c_uint]),
         "pcmx_raycast_serial": (None, [P, P, I, I, P]),
         "pcmx_spmv_csr_omp": (None, [I, P, P, P, P, P]),
+        "pcmx_spmm_csr_omp": (None, [I, P, P, P, P, LL, P, LL, I]),
         "pcmx_band_ranges": (None, [I, I, I, I, I, I, I, P, P]),
         "pcmx_powerlaw_row_counts": (LL, [I, LL, D, ctypes.c_ulonglong, P]),
         "pcmx_powerlaw_fill": (None, [I, I, P, ctypes.c_ulonglong, P, P]),

@@ -1811,7 +1811,91 @@ class SetOps(Workload):
         return {"elements_checked": self.a.numel() + self.b.numel(), "kept": k, "exact_vs_torch": ok, "check_passed": ok}
 
 
-WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV,
+class SpMM(Workload):
+    """Y = A X for a CSR matrix and a dense block of k vectors per GPU (csrc/kernels/spmm.hip, ops.spmm). matrix
+    "powerlaw" (ops.powerlaw_csr(n_rows, nnz)), "banded" (the reference's 5-band geometry 401 200 100 200 10 on n_rows
+    rows; nnz follows) or "uniform" (every row round(nnz / n_rows) nonzeros in uniformly drawn columns). item_nnz: the
+    plan's item size (None: ops.spmm's default for k). GFLOP/s = 2 nnz k / time. No communication (weak scaling).
+    csr: a prebuilt matrix to use instead."""
+
+    MATRICES = ("powerlaw", "banded", "uniform")
+    BAND = (401, 200, 100, 200, 10)
+    SAMPLE = 2048  # rows the check compares with fp64
+
+    def __init__(self, ctx, n_rows=1_000_000, nnz=10_000_000, k=64, matrix="powerlaw", item_nnz=None, csr=None, **_):
+        n_rows, nnz, k = int(n_rows), int(nnz), int(k)
+        if matrix not in self.MATRICES:
+            raise ValueError(f"spmm matrix {matrix!r}: one of {self.MATRICES}")
+        if n_rows < 1 or k < 1 or nnz < 0:
+            raise ValueError(f"spmm n_rows = {n_rows}, nnz = {nnz}, k = {k}: at least one row and column, nnz >= 0")
+        if csr is not None:  # a prebuilt ops.CSR (scripts/spmm_lab.py shares one matrix between its cases)
+            m, n_rows = csr, csr.n_rows
+        elif matrix == "powerlaw":
+            m = ops.powerlaw_csr(n_rows, nnz, seed=1 + ctx.rank)
+        elif matrix == "banded":
+            if n_rows < 2048:
+                raise ValueError("spmm matrix 'banded': at least 2048 rows (the bands reach 710 columns)")
+            m = ops.banded_csr(n_rows, *self.BAND)
+        else:
+            g = torch.Generator().manual_seed(25000 + ctx.rank)
+            per_row = max(1, round(nnz / n_rows))
+            rp = torch.arange(n_rows + 1, dtype=torch.int64) * per_row
+            col = torch.randint(0, n_rows, (n_rows * per_row,), generator=g, dtype=torch.int32)
+            m = ops.CSR(rp, col, torch.rand(n_rows * per_row, generator=g) * 2 - 1, n_rows)
+        self.item_nnz = ops.sparse.spmm_item_nnz(k) if item_nnz is None else int(item_nnz)
+        super().__init__(ctx, {"n_rows": n_rows, "nnz": m.nnz, "k": k, "matrix": matrix, "item_nnz": self.item_nnz},
+                         "spmm", "GFLOP/s")
+        self.m = m if m.val.device == torch.device(ctx.device) else m.to(ctx.device)
+        g = torch.Generator(device=ctx.device).manual_seed(25100 + ctx.rank)
+        self.x = torch.rand(m.n_cols, k, device=ctx.device, generator=g) * 2 - 1
+        self.out = torch.empty(n_rows, k, device=ctx.device)
+        if self.x.is_cuda:
+            self.m.spmm_plan(self.item_nnz)  # the host analysis, once per matrix: outside the timed steps
+
+    def step(self):
+        ops.spmm(self.m, self.x, out=self.out, item_nnz=self.item_nnz)
+
+    def work_per_step(self):
+        return 2.0 * self.m.nnz * self.x.shape[1]
+
+    def compulsory_bytes(self) -> int:
+        """col and val read once, X read once, Y written once."""
+        return 8 * self.m.nnz + 4 * self.x.shape[1] * (self.m.n_cols + self.m.n_rows)
+
+    def check(self, reduce: bool = True):
+        """A fixed seeded sample of rows (with the first, the last and the longest row) against the fp64 product: every
+        entry within the any-order bound len u / (1 - len u) * sum|v x| (u = 2^-24; one rounding per product and per
+        addition, whatever the order), an empty row exactly 0. Local only."""
+        m, k = self.m, self.x.shape[1]
+        lens = m.row_ptr[1:] - m.row_ptr[:-1]
+        g = torch.Generator().manual_seed(25200)
+        rows = torch.randint(0, m.n_rows, (min(self.SAMPLE, m.n_rows),), generator=g)
+        rows = torch.unique(torch.cat([rows, torch.tensor([0, m.n_rows - 1, int(lens.argmax())])])).to(lens.device)
+        ln = lens[rows]
+        seg = torch.repeat_interleave(torch.arange(rows.numel(), device=ln.device), ln)
+        nz = torch.arange(seg.numel(), device=ln.device) - (ln.cumsum(0) - ln)[seg] + m.row_ptr[rows][seg]
+        v, c = m.val[nz].double()[:, None], m.col[nz].long()
+        worst, ok = 0.0, True
+        ku = (ln.double() * 2.0 ** -24)[:, None]
+        for c0 in range(0, k, 32):
+            prod = v * self.x[c, c0:c0 + 32].double()
+            ref = torch.zeros(rows.numel(), prod.shape[1], dtype=torch.float64, device=prod.device).index_add_(0, seg, prod)
+            bound = ku / (1 - ku) * torch.zeros_like(ref).index_add_(0, seg, prod.abs())
+            err = (self.out[rows, c0:c0 + 32].double() - ref).abs()
+            ok = ok and bool((err <= bound).all())
+            worst = max(worst, float((err / bound.clamp_min(1e-300))[bound > 0].max()) if bool((bound > 0).any()) else 0.0)
+        if reduce:
+            ok = self.ctx.max_over_ranks(0.0 if ok else 1.0) == 0.0
+        return {"rows_checked": int(rows.numel()), "worst_err_over_bound": worst, "check_passed": bool(ok)}
+
+    def report(self, seconds: float, steps: int) -> dict:
+        rep = super().report(seconds, steps)
+        rep["compulsory_gb_per_s"] = self.ctx.world * self.compulsory_bytes() * steps / seconds / 1e9
+        rep["gathered_gb_per_s"] = self.ctx.world * 4.0 * self.m.nnz * self.x.shape[1] * steps / seconds / 1e9
+        return rep
+
+
+WORKLOADS = {"sgemm": Sgemm, "reduce": Reduce, "scan": Scan, "stencil": Stencil, "spmv": SpMV, "spmm": SpMM,
              "region3d": Region3D, "raycast": Raycast, "histeq": Histeq, "region2d": Region2D, "select": Select,
              "sort": Sort, "segreduce": SegReduce, "topk": TopK, "scanbykey": ScanByKey, "bincount": Bincount,
              "merge": Merge, "rowsort": RowSort, "axis": Axis, "ragged": Ragged, "segsort": SegSort,

@@ -3,7 +3,7 @@ from .gemm import sgemm, sgemm_naive_host, sgemm_out, sgemm_simt
 from .halo import pack_edges, unpack_halo_
 from .image import (SEED_3D, Camera, apply_region_mask, corner_seeds, create_volume, default_camera, histeq, pad1,
                     raycast, region2d, region2d_grow_padded_, region3d)
-from .sparse import CSR, SlicedCSR, banded_csr, create_vector, powerlaw_csr, spmv, spmv_banded
+from .sparse import CSR, SlicedCSR, banded_csr, create_vector, powerlaw_csr, spmm, spmv, spmv_banded
 from .stencil import init_grid, stencil5_reference, stencil5_step_, stencil5x2_step_, stencil5_fused_step_, stencil5_fused_spans_
 # sort_keys / sort / argsort / sort_by_key / topk / kth_value take dim=int for the row-wise forms (one wave or one block
 # per row, csrc/kernels/rowsort.hip); their route constants (ROWSORT_*, ROW_TOPK_*) live in .vector. reduce / scan take
@@ -30,7 +30,7 @@ __all__ = [
     "histeq", "region2d", "region2d_grow_padded_", "region3d", "corner_seeds", "pad1", "apply_region_mask",
     "create_volume", "raycast", "default_camera", "Camera", "SEED_3D",
     "stencil5_step_", "stencil5x2_step_", "stencil5_fused_step_", "stencil5_fused_spans_", "stencil5_reference", "init_grid",
-    "CSR", "SlicedCSR", "banded_csr", "create_vector", "powerlaw_csr", "spmv", "spmv_banded",
+    "CSR", "SlicedCSR", "banded_csr", "create_vector", "powerlaw_csr", "spmm", "spmv", "spmv_banded",
     "pack_edges", "unpack_halo_",
     "compact", "select", "compact_indices", "select_indices", "compact_where", "CMP_CODES",
     "sort_keys", "sort", "argsort", "sort_by_key", "topk", "kth_value",

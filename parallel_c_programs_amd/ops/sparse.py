@@ -7,7 +7,7 @@ north-star 1e8-nnz power-law graph) and a banded kernel without column indices.
 from __future__ import annotations
 
 import ctypes
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import torch
 
@@ -21,6 +21,7 @@ class CSR:
     val: torch.Tensor      # float32 [nnz]
     n_cols: int
     items: torch.Tensor | None = None  # GPU work items (int64 [k, 3]), built by plan()
+    spmm_plans: dict = field(default_factory=dict, repr=False, compare=False)  # (item_nnz, device) -> SpmmPlan
 
     @property
     def n_rows(self) -> int:
@@ -42,6 +43,21 @@ class CSR:
         self.items = items.to(self.row_ptr.device)
         return self
 
+    def spmm_plan(self, item_nnz: int, device=None) -> "SpmmPlan":
+        """The SpMM plan for items of at most item_nnz nonzeros (host analysis, once per matrix, item size and device;
+        cached beside `items`)."""
+        from .. import _C
+
+        device = torch.device(self.val.device if device is None else device)
+        key = (int(item_nnz), str(device))
+        if key not in self.spmm_plans:
+            if item_nnz % 64 or not 64 <= item_nnz <= 1024:
+                raise ValueError(f"item_nnz must be a multiple of 64 in 64..1024, got {item_nnz}")
+            items, slot, split = _C.spmm_csr_plan(self.row_ptr.cpu().contiguous(), int(item_nnz))
+            self.spmm_plans[key] = SpmmPlan(int(item_nnz), items.to(device), slot.to(device), split.to(device),
+                                            int(split[:, 2].sum()))
+        return self.spmm_plans[key]
+
     def row_block(self, r0: int, r1: int) -> "CSR":
         """Rows [r0, r1) as their own CSR (views of col/val; the work-item plan is rebuilt on demand)."""
         a, b = int(self.row_ptr[r0]), int(self.row_ptr[r1])
@@ -53,6 +69,16 @@ class CSR:
         d = torch.zeros(self.n_rows, self.n_cols, dtype=torch.float32, device=self.val.device)
         d.index_put_((rows, self.col.long()), self.val, accumulate=True)
         return d
+
+
+@dataclass
+class SpmmPlan:
+    """What the SpMM kernels read besides the CSR arrays (csrc/kernels/spmm.hip)."""
+    item_nnz: int
+    items: torch.Tensor  # int64 [n, 3]: row0 | row1 << 32, nz0, nz1 (the SpMV planner's nnz-balanced items)
+    slot: torch.Tensor   # int32 [n]: workspace slot of a piece of a split row, -1 for every other item
+    split: torch.Tensor  # int32 [s, 3]: (row, first slot, pieces) per split row
+    n_pieces: int        # workspace rows
 
 
 class PackedLayoutUnavailable(ValueError):
@@ -425,6 +451,71 @@ def spmv(m: CSR, x: torch.Tensor) -> torch.Tensor:
     cpu_lib().pcmx_spmv_csr_omp(m.n_rows, rp32.data_ptr(), m.col.data_ptr(), m.val.data_ptr(),
                                 x.contiguous().data_ptr(), y.data_ptr())
     return y
+
+
+def spmm_item_nnz(k: int) -> int:
+    """The item size ops.spmm plans with by default, per width class: the wider the dense block, the more a nonzero
+    gathers (4 k bytes), so the fewer nonzeros make a wave's fair share of the work (profiles/r25_spmm/)."""
+    return 1024 if k <= 32 else 128 if k <= 64 else 256
+
+
+def spmm(m: CSR, x: torch.Tensor, out: torch.Tensor | None = None, item_nnz: int | None = None) -> torch.Tensor:
+    """Y[n_rows, k] = A X[n_cols, k] in float32, X and Y row-major (GPU: csrc/kernels/spmm.hip, one wave per work item
+    and column tile, the lanes across the dense columns; CPU tensors: the host library, OpenMP over rows).
+
+    Contract:
+      1. Reproducibility: the bits of Y depend only on the matrix, the plan's item size (`item_nnz`, default by k:
+         spmm_item_nnz), k and the data; the same on every call and every stream. No float atomics: the pieces of a row
+         longer than the item size are summed in ascending piece order by a fix-up launch.
+      2. Column independence: column c of Y depends only on column c of X. spmm(m, X[:, perm]) equals
+         spmm(m, X)[:, perm] bit for bit; a NaN or inf in X[j, c] reaches exactly the Y[r, c] of the rows r that store
+         column j; the masked lanes of a partial column tile load and store nothing.
+      3. An empty row gives +0.0 in all k columns; an empty matrix, n_rows == 0 and k == 0 give results of the right
+         shape without a launch. The padding of `out` between k and its row stride, and anything past its last row, is
+         not touched.
+      4. X: 2-D float32 with shape[0] == n_cols on the matrix's device. A view with stride(1) == 1 and a row stride
+         >= k (sliced columns, a storage offset, an odd leading dimension) is read where it lies; anything else is made
+         contiguous. `out`: float32 [n_rows, k], stride(1) == 1, row stride >= k, not sharing storage with X. TypeError
+         for a wrong dtype, ValueError for a 1-D X, a shape or device mismatch, an overlapping `out` and an item_nnz
+         that is no multiple of 64 in 64..1024 — all before any launch. `col` is trusted, as in spmv.
+    Base addresses and leading dimensions that are multiples of the vector (2 floats for 64 < k <= 128 tiles, 4 above)
+    take the float2 / float4 kernels, anything else the same tiles with dword accesses; the values are the same."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError(f"x must be a float32 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 2 or x.shape[0] != m.n_cols:
+        raise ValueError(f"x must be 2-D [n_cols = {m.n_cols}, k], got shape {tuple(x.shape)}")
+    if x.device != m.val.device:
+        raise ValueError(f"x is on {x.device}, the matrix on {m.val.device}")
+    n_rows, k = m.n_rows, x.shape[1]
+    if item_nnz is None:
+        item_nnz = spmm_item_nnz(k)
+    if int(item_nnz) % 64 or not 64 <= int(item_nnz) <= 1024:
+        raise ValueError(f"item_nnz must be a multiple of 64 in 64..1024, got {item_nnz}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+            raise TypeError(f"out must be a float32 tensor, got {getattr(out, 'dtype', type(out))}")
+        if out.shape != (n_rows, k):
+            raise ValueError(f"out must have shape {(n_rows, k)}, got {tuple(out.shape)}")
+        if out.device != x.device:
+            raise ValueError(f"out is on {out.device}, x on {x.device}")
+        if (k > 1 and out.stride(1) != 1) or (n_rows > 1 and out.stride(0) < k):
+            raise ValueError(f"out needs stride(1) == 1 and a row stride >= k, got strides {out.stride()}")
+        if out.numel() and x.numel() and out.untyped_storage().data_ptr() == x.untyped_storage().data_ptr():
+            raise ValueError("out shares storage with x")
+    else:
+        out = torch.empty(n_rows, k, dtype=torch.float32, device=x.device)
+    if (k > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < k):
+        x = x.contiguous()
+    if n_rows == 0 or k == 0:
+        return out
+    if x.is_cuda:
+        p = m.spmm_plan(int(item_nnz), x.device)
+        return ops().spmm_csr(m.row_ptr, m.col, m.val, x, p.items, p.slot, p.split, p.n_pieces, p.item_nnz, out)
+    ldx = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), k)
+    ldy = out.stride(0) if n_rows > 1 else max(out.stride(0), k)
+    cpu_lib().pcmx_spmm_csr_omp(n_rows, m.row_ptr.contiguous().data_ptr(), m.col.contiguous().data_ptr(),
+                                m.val.contiguous().data_ptr(), x.data_ptr(), ldx, out.data_ptr(), ldy, k)
+    return out
 
 
 def sort_csr_columns(row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, max_len: int | None = None):
